@@ -2,7 +2,7 @@
 """bench.py -- headline benchmark of the hot path (BASELINE.json): 2-D TV-L1 Douglas-Rachford, 4096x4096 float64,
 lambda = 0.1, 35 pinned iterations, on MI355X.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
 
 One "step" = one complete DR solve (DR2_TV semantics, through the C-ABI's device-pointer entry point) of one
 synthetic 4096x4096 image that is already resident in HBM; the result stays in HBM.  With N > 1 (one process per
@@ -10,15 +10,21 @@ GPU, launched by torch.distributed.run) every rank solves its own independent im
 over images with no collective in the data path ("scaling": "weak"); value = pixels all ranks processed / max-over-
 ranks wall time.  Rank 0 prints ONE JSON line.
 
-Extra objects on that line:
+A plain run does only what the headline needs: set-up, W warm-up solves, the K timed solves, and the line (metric, value, unit,
+ms_per_step, step_ms, config, and the part of `roofline` that follows from ms_per_step alone).  --dump-outputs DIR also writes what
+the LAST timed solve returned as DIR/<name>.npy (dump_outputs below); the inputs are seeded, so two builds run with the same
+arguments can be compared output for output.  Whatever else this file measures or checks takes runs of its own and happens only
+with --full.
+
+Extra objects on the line of a --full run:
   roofline     -- the dominant sweep kernel: algorithmic HBM bytes per launch / average launch duration, measured
-                  with hipEvents on the library's own stream during K further solves right after the timed ones (the
+                  with hipEvents on the library's own stream during K further solves after the timed ones (the
                   events cost ~0.8 ms per solve, so they stay out of the timed region; DESIGN.md "Measurement");
                   `by_kernel` = the same fraction for every sweep flavour (DR_COL, DR_ROW inside the solve; plain OP_PROX
                   sweeps in both directions measured on their own), `solve_frac` = the whole solve's algorithmic bytes
                   / ms_per_step / peak; `traffic` = PMC-measured HBM bytes per launch from profiles/, or null when that
                   file was measured on another build of the kernels (build id = hash of the kernel sources).
-  step_ms      -- min / median / max of the K timed steps.
+  output_check -- the last timed solve's result against the compiled reference's digest in tests/golden/golden_large.npz.
   c5           -- BASELINE config #5 per rank: 64 independent 2048x2048 images through proxtv_DR2_TV_batch_dev, solver
                   time and (N > 1) the RCCL gather to rank 0 timed separately.
   c3, c4, hard, lambda_1 -- the other BASELINE configurations and two neighbours of the headline, clocked by whoever runs this file
@@ -172,14 +178,19 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=2)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-others", action="store_true", help="skip the c3 / c4 / hard / lambda_1 objects")
-    ap.add_argument("--no-c5", action="store_true", help="skip the config-#5 object (64 x 2048^2 per rank, ~13 GiB of HBM)")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write what the last timed step returned as DIR/<name>.npy")
+    ap.add_argument("--full", action="store_true", help="after the timed steps also run every other leg: output check, end-to-end, "
+                    "per-kernel roofline, config #5, c3 / c4 / hard / lambda_1, the CPU baseline (the --no-* options below trim it)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the cpu_baseline object")
+    ap.add_argument("--no-others", action="store_true", help="--full without the c3 / c4 / hard / lambda_1 objects")
+    ap.add_argument("--no-c5", action="store_true", help="--full without the config-#5 object (64 x 2048^2 per rank, ~13 GiB of HBM)")
     ap.add_argument("--no-gather", action="store_true", help="config #5 without the final gather to rank 0 (solver scaling and "
                     "gather time separable on a multi-GPU node)")
     ap.add_argument("--c5-images", type=int, default=64, help="images per rank of the config-#5 object (BASELINE: 64; the "
                     "shared-GPU plumbing test uses fewer)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
 
     import torch
     import torch.distributed as dist
@@ -232,6 +243,65 @@ def main():
     dt = time.perf_counter() - t0
     assert int(info[0]) == ITERS, info
 
+    # who took part: what the process group itself reports, and every rank's device (rank 0 prints them)
+    ranks_info = [{"rank": 0, "device": torch.cuda.get_device_name(torch.cuda.current_device()), "index": torch.cuda.current_device()}]
+    if world > 1:
+        t = torch.tensor([dt], dtype=torch.float64, device="cpu" if shared else "cuda")
+        dist.all_reduce(t, op=dist.ReduceOp.MAX)
+        dt = float(t.item())
+        mine = {"rank": rank, "device": torch.cuda.get_device_name(torch.cuda.current_device()), "index": torch.cuda.current_device()}
+        ranks_info = [None] * world
+        dist.all_gather_object(ranks_info, mine)
+        assert dist.get_world_size() == world
+    ms_per_step = dt / args.steps * 1e3
+
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, yd, info, "" if world == 1 else f"_rank{rank}")
+
+    # ---- every other leg takes runs of its own: only on request, after the timed region and the dump ---------------------------------
+    extra = full_legs(args, torch, dist, device, lib, world, rank, shared, barrier, x_host, xd, yd) if args.full else {}
+
+    if rank == 0:
+        solve_bytes = 8 * M * N * (6 * ITERS + 7)          # SURVEY 8(d): 1736 B/pixel at 35 iterations
+        roofline = {"bound": "hbm", "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                    "solve_frac": (solve_bytes / (ms_per_step * 1e-3) / 1e9) / HBM_PEAK_GBS, "solve_algorithmic_bytes": solve_bytes}
+        roofline.update(extra.pop("roofline", {}))
+        line = {
+            "metric": "Mpixel/s on 2D TV-L1 DR (4096x4096 f64, lambda=0.1); % HBM roofline",
+            "value": world * M * N * args.steps / dt / 1e6, "unit": "Mpixel/s", "n_gpus": world, "steps": args.steps,
+            "warmup": args.warmup, "ms_per_step": ms_per_step, "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
+            "dtype": "f64", "data": "synthetic", "full": bool(args.full),
+            "config": {"workload": "tv1_2d (DR2_TV, 35 iterations) on one 4096x4096 float64 N(0,1) image per GPU per step, "
+                                   "lambda=0.1, input and output resident in HBM", "images_per_step": world,
+                       "parallelism": f"independent images, {world} rank(s), no data-path collective",
+                       "process_group": {"world_size": dist.get_world_size() if world > 1 else 1,
+                                         "backend": dist.get_backend() if world > 1 else None, "ranks": ranks_info}},
+            "roofline": roofline,
+            "step_ms": {"min": min(step_t) * 1e3, "median": float(np.median(step_t)) * 1e3, "max": max(step_t) * 1e3},
+        }
+        line.update(extra)
+        print(json.dumps(line), flush=True)
+
+    if world > 1:
+        dist.barrier()
+        dist.destroy_process_group()
+
+
+def dump_outputs(path, yd, info, suffix):
+    """What a caller of the timed path holds after the last timed step, as float64 .npy files: `info` (the solver's three status
+    numbers) whole, and of the 4096x4096 result (134 MB) a fixed sample -- 2^22 positions of its column-major storage drawn once
+    from a seeded generator, the same for every run and every build, 32 MiB."""
+    import torch
+    os.makedirs(path, exist_ok=True)
+    idx = np.random.default_rng(4096).integers(0, M * N, size=1 << 22)
+    flat = yd.permute(1, 0).reshape(-1)                       # column-major storage order (the permuted view is contiguous)
+    sample = flat[torch.from_numpy(idx).to(flat.device)].cpu().numpy()
+    np.save(os.path.join(path, f"y_sample{suffix}.npy"), sample.astype(np.float64, copy=False))
+    np.save(os.path.join(path, f"info{suffix}.npy"), np.asarray(info, dtype=np.float64))
+
+
+def full_legs(args, torch, dist, device, lib, world, rank, shared, barrier, x_host, xd, yd):
+    """The legs of a --full run, in the order they always ran; returns the objects they add to rank 0's line."""
     # ---- did the timed solves do the work?  Rank 0's input is default_rng(0).standard_normal((4096, 4096)) -- exactly the `c2` fixture
     # of tests/golden/golden_large.npz, a digest (strided subsample + moments) of what the compiled reference returns for it -- so the
     # output of the LAST timed solve is compared with that digest here, outside the timed region.  (Data only: nothing under oracle/.)
@@ -345,97 +415,70 @@ def main():
         del xd, yd
         others = other_configs(device, torch, np.load(os.path.join(ROOT, "tests", "golden", "golden_large.npz")))
 
-    # who took part: what the process group itself reports, and every rank's device (rank 0 prints them)
-    ranks_info = [{"rank": 0, "device": torch.cuda.get_device_name(torch.cuda.current_device()), "index": torch.cuda.current_device()}]
-    if world > 1:
-        t = torch.tensor([dt], dtype=torch.float64, device="cpu" if shared else "cuda")
-        dist.all_reduce(t, op=dist.ReduceOp.MAX)
-        dt = float(t.item())
-        mine = {"rank": rank, "device": torch.cuda.get_device_name(torch.cuda.current_device()), "index": torch.cuda.current_device()}
-        ranks_info = [None] * world
-        dist.all_gather_object(ranks_info, mine)
-        assert dist.get_world_size() == world
+    if rank != 0:
+        return {}
+    # dominant kernel family and its algorithmic traffic per launch: column sweep R t, W s' = 16 B/px;
+    # fused row sweep R s', R U, R t, W t = 32 B/px
+    per_px = {0: 16, 1: 32}
+    dom = 0 if fam_ms[0] >= fam_ms[1] else 1
+    avg_ms = fam_ms[dom] / max(fam_n[dom], 1)
+    achieved = per_px[dom] * M * N / (avg_ms * 1e-3) / 1e9 if avg_ms > 0 else 0.0
 
-    if rank == 0:
-        ms_per_step = dt / args.steps * 1e3
-        value = world * M * N * args.steps / dt / 1e6
-        # dominant kernel family and its algorithmic traffic per launch: column sweep R t, W s' = 16 B/px;
-        # fused row sweep R s', R U, R t, W t = 32 B/px
-        per_px = {0: 16, 1: 32}
-        dom = 0 if fam_ms[0] >= fam_ms[1] else 1
-        avg_ms = fam_ms[dom] / max(fam_n[dom], 1)
-        achieved = per_px[dom] * M * N / (avg_ms * 1e-3) / 1e9 if avg_ms > 0 else 0.0
+    def frac(bytes_per_px, ms):
+        return (bytes_per_px * M * N / (ms * 1e-3) / 1e9) / HBM_PEAK_GBS if ms > 0 else None
+    by_kernel = {
+        "DR_COL": {"bytes_per_px": 16, "avg_launch_ms": fam_ms[0] / max(fam_n[0], 1), "frac": frac(16, fam_ms[0] / max(fam_n[0], 1))},
+        "DR_ROW": {"bytes_per_px": 32, "avg_launch_ms": fam_ms[1] / max(fam_n[1], 1), "frac": frac(32, fam_ms[1] / max(fam_n[1], 1))},
+        "PROX_COL": {"bytes_per_px": 16, "avg_launch_ms": prox_ms["prox_col"], "frac": frac(16, prox_ms["prox_col"])},
+        "PROX_ROW": {"bytes_per_px": 16, "avg_launch_ms": prox_ms["prox_row"], "frac": frac(16, prox_ms["prox_row"])},
+    }
+    # HBM bytes per launch from the PMC run of this same command (tools/pmc_traffic.py: FETCH_SIZE + WRITE_SIZE,
+    # separate passes, calibrated on an 8-B/lane copy of known size).  bench.py cannot run under the profiler
+    # itself, so the figure is read from profiles/ -- and only if it was measured on THIS build of the kernels.
+    traffic = None
+    traffic_source = None
+    try:
+        from proxtv_amd import build as _build
+        import glob
+        pmc = {}
+        for path in sorted(glob.glob(os.path.join(ROOT, "profiles", "r*_pmc_traffic.json")), reverse=True):   # newest round first
+            with open(path) as f:
+                cand = json.load(f)
+            if cand.get("build_id") == _build.build_id():
+                pmc = cand
+                break
+        if pmc:
+            label = ["column sweep (DR_COL)", "row sweep (DR_ROW)"][dom]
+            traffic = pmc["kernels"][label]["hbm_total"]
+            traffic_source = (f"{os.path.relpath(path, ROOT)}: rocprofv3 --pmc passes of this workload run by the builder on build "
+                              f"{pmc.get('build_id')} (= this build); not measured by this run -- bench.py cannot profile itself")
+    except (OSError, KeyError, ValueError):
+        pass
+    extra = {
+        # (main() adds bound / peak / unit / solve_frac / solve_algorithmic_bytes, which need no run of their own)
+        "roofline": {"kernel": ["column sweep (DR_COL)", "row sweep (DR_ROW, fused reflections+combiner)"][dom],
+                     "achieved": achieved, "frac": achieved / HBM_PEAK_GBS,
+                     "traffic": traffic, "traffic_source": traffic_source, "avg_launch_ms": avg_ms, "launches": fam_n[dom],
+                     "measured": f"hipEvents around every sweep launch during {args.steps} further solves of the same input "
+                                 f"({dt_events / args.steps * 1e3:.2f} ms per solve with the events in the stream; every event pair serialises its "
+                                 f"launch, tail included, so family_ms_per_solve sums to slightly MORE than ms_per_step of the un-instrumented solves)",
+                     "algorithmic_bytes_per_launch": per_px[dom] * M * N,
+                     "family_ms_per_solve": {"col": fam_ms[0] / args.steps, "row": fam_ms[1] / args.steps,
+                                             "other": fam_ms[2] / args.steps},
+                     "by_kernel": by_kernel},
+        "output_check": output_check,
+        "end_to_end_ms": end_to_end_ms,
+        "end_to_end": {"ms": end_to_end_ms, "value": M * N / end_to_end_ms / 1e3, "unit": "Mpixel/s",
+                       "what": "DR2_TV through the host-pointer C-ABI: pageable numpy in, numpy out (2 x 134 MB over the link + the solve)"},
+    }
+    if c5 is not None:
+        extra["c5"] = c5
+    if others:
+        extra.update(others)
+    if world == 1 and not args.no_cpu_baseline:
+        extra["cpu_baseline"] = cpu_baseline()
+    return extra
 
-        def frac(bytes_per_px, ms):
-            return (bytes_per_px * M * N / (ms * 1e-3) / 1e9) / HBM_PEAK_GBS if ms > 0 else None
-        by_kernel = {
-            "DR_COL": {"bytes_per_px": 16, "avg_launch_ms": fam_ms[0] / max(fam_n[0], 1), "frac": frac(16, fam_ms[0] / max(fam_n[0], 1))},
-            "DR_ROW": {"bytes_per_px": 32, "avg_launch_ms": fam_ms[1] / max(fam_n[1], 1), "frac": frac(32, fam_ms[1] / max(fam_n[1], 1))},
-            "PROX_COL": {"bytes_per_px": 16, "avg_launch_ms": prox_ms["prox_col"], "frac": frac(16, prox_ms["prox_col"])},
-            "PROX_ROW": {"bytes_per_px": 16, "avg_launch_ms": prox_ms["prox_row"], "frac": frac(16, prox_ms["prox_row"])},
-        }
-        solve_bytes = 8 * M * N * (6 * ITERS + 7)          # SURVEY 8(d): 1736 B/pixel at 35 iterations
-        # HBM bytes per launch from the PMC run of this same command (tools/pmc_traffic.py: FETCH_SIZE + WRITE_SIZE,
-        # separate passes, calibrated on an 8-B/lane copy of known size).  bench.py cannot run under the profiler
-        # itself, so the figure is read from profiles/ -- and only if it was measured on THIS build of the kernels.
-        traffic = None
-        traffic_source = None
-        try:
-            from proxtv_amd import build as _build
-            import glob
-            pmc = {}
-            for path in sorted(glob.glob(os.path.join(ROOT, "profiles", "r*_pmc_traffic.json")), reverse=True):   # newest round first
-                with open(path) as f:
-                    cand = json.load(f)
-                if cand.get("build_id") == _build.build_id():
-                    pmc = cand
-                    break
-            if pmc:
-                label = ["column sweep (DR_COL)", "row sweep (DR_ROW)"][dom]
-                traffic = pmc["kernels"][label]["hbm_total"]
-                traffic_source = (f"{os.path.relpath(path, ROOT)}: rocprofv3 --pmc passes of this workload run by the builder on build "
-                                  f"{pmc.get('build_id')} (= this build); not measured by this run -- bench.py cannot profile itself")
-        except (OSError, KeyError, ValueError):
-            pass
-        line = {
-            "metric": "Mpixel/s on 2D TV-L1 DR (4096x4096 f64, lambda=0.1); % HBM roofline",
-            "value": value, "unit": "Mpixel/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-            "ms_per_step": ms_per_step, "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
-            "dtype": "f64", "data": "synthetic",
-            "config": {"workload": "tv1_2d (DR2_TV, 35 iterations) on one 4096x4096 float64 N(0,1) image per GPU per step, "
-                                   "lambda=0.1, input and output resident in HBM", "images_per_step": world,
-                       "parallelism": f"independent images, {world} rank(s), no data-path collective",
-                       "process_group": {"world_size": dist.get_world_size() if world > 1 else 1,
-                                         "backend": dist.get_backend() if world > 1 else None, "ranks": ranks_info}},
-            "roofline": {"bound": "hbm", "kernel": ["column sweep (DR_COL)", "row sweep (DR_ROW, fused reflections+combiner)"][dom],
-                         "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": achieved / HBM_PEAK_GBS,
-                         "traffic": traffic, "traffic_source": traffic_source, "avg_launch_ms": avg_ms, "launches": fam_n[dom],
-                         "measured": f"hipEvents around every sweep launch during {args.steps} further solves of the same input "
-                                     f"({dt_events / args.steps * 1e3:.2f} ms per solve with the events in the stream; every event pair serialises its "
-                                     f"launch, tail included, so family_ms_per_solve sums to slightly MORE than ms_per_step of the un-instrumented solves)",
-                         "algorithmic_bytes_per_launch": per_px[dom] * M * N,
-                         "family_ms_per_solve": {"col": fam_ms[0] / args.steps, "row": fam_ms[1] / args.steps,
-                                                 "other": fam_ms[2] / args.steps},
-                         "by_kernel": by_kernel,
-                         "solve_frac": (solve_bytes / (ms_per_step * 1e-3) / 1e9) / HBM_PEAK_GBS,
-                         "solve_algorithmic_bytes": solve_bytes},
-            "output_check": output_check,
-            "step_ms": {"min": min(step_t) * 1e3, "median": float(np.median(step_t)) * 1e3, "max": max(step_t) * 1e3},
-            "end_to_end_ms": end_to_end_ms,
-            "end_to_end": {"ms": end_to_end_ms, "value": M * N / end_to_end_ms / 1e3, "unit": "Mpixel/s",
-                           "what": "DR2_TV through the host-pointer C-ABI: pageable numpy in, numpy out (2 x 134 MB over the link + the solve)"},
-        }
-        if c5 is not None:
-            line["c5"] = c5
-        if others:
-            line.update(others)
-        if world == 1 and not args.no_cpu_baseline:
-            line["cpu_baseline"] = cpu_baseline()
-        print(json.dumps(line), flush=True)
-
-    if world > 1:
-        dist.barrier()
-        dist.destroy_process_group()
 
 
 if __name__ == "__main__":

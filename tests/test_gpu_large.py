@@ -144,6 +144,39 @@ def test_c5_full_shard_one_batched_call(glarge):
     assert float((yb - xb).abs().max()) <= 0.4 + 1e-6
 
 
+def test_bench_plain_run_and_dump(ptv, tmp_path):
+    """A plain bench.py run times its steps and prints the headline only (every other leg needs --full), and --dump-outputs
+    writes what the last timed solve returned: `info` and the seeded sample of the result, equal bit for bit to the same
+    solve through the Python surface."""
+    import json
+    import os
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1",
+           "--dump-outputs", str(tmp_path / "dump")]
+    out = subprocess.run(cmd, cwd=root, capture_output=True, text=True, timeout=300)
+    assert out.returncode == 0, out.stderr[-3000:]
+    lines = [ln for ln in out.stdout.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1, out.stdout[-2000:]
+    d = json.loads(lines[0])
+    assert d["steps"] == 3 and d["warmup"] == 1 and d["n_gpus"] == 1 and d["full"] is False
+    assert d["unit"] == "Mpixel/s" and d["higher_is_better"] is True and d["dtype"] == "f64"
+    assert d["value"] == pytest.approx(4096 * 4096 / (d["ms_per_step"] * 1e-3) / 1e6, rel=1e-6)
+    assert 0 < d["step_ms"]["min"] <= d["ms_per_step"]        # the K stamped solves lie inside the timed region
+    for leg in ("output_check", "end_to_end", "c5", "c3", "c4", "hard", "lambda_1", "cpu_baseline"):
+        assert leg not in d, leg
+    assert "by_kernel" not in d["roofline"] and 0 < d["roofline"]["solve_frac"] < 1
+    files = sorted(os.listdir(tmp_path / "dump"))
+    assert files == ["info.npy", "y_sample.npy"]
+    info, sample = np.load(tmp_path / "dump" / "info.npy"), np.load(tmp_path / "dump" / "y_sample.npy")
+    assert info.dtype == np.float64 and info[0] == 35
+    assert sample.dtype == np.float64 and sample.shape == (1 << 22,) and info.nbytes + sample.nbytes <= 64 * 10**6
+    X = np.asfortranarray(np.random.default_rng(0).standard_normal((4096, 4096)))   # rank 0's input
+    idx = np.random.default_rng(4096).integers(0, 4096 * 4096, size=1 << 22)
+    np.testing.assert_array_equal(sample, ptv.tv1_2d(X, 0.1).ravel(order="F")[idx])
+
+
 def test_bench_two_ranks_on_one_gpu_dry_run():
     """bench.py's N > 1 path end to end on a one-GPU box: torch.distributed.run, two ranks sharing device 0
     (PROXTV_BENCH_SHARED_GPU=1: gloo instead of RCCL -- plumbing, not a measurement).  Exercises the rank environment, the
@@ -160,7 +193,7 @@ def test_bench_two_ranks_on_one_gpu_dry_run():
     env = dict(os.environ, PROXTV_BENCH_SHARED_GPU="1")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
            "--master-port", str(port), os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1",
-           "--c5-images", "4"]
+           "--full", "--c5-images", "4"]
     out = subprocess.run(cmd, env=env, cwd=root, capture_output=True, text=True, timeout=600)
     assert out.returncode == 0, out.stderr[-3000:]
     lines = [ln for ln in out.stdout.splitlines() if ln.startswith("{")]
@@ -196,7 +229,8 @@ def test_bench_two_ranks_full_shard_and_no_gather():
             s.bind(("127.0.0.1", 0))
             port = s.getsockname()[1]
         cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
-               "--master-port", str(port), os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "1", "--warmup", "1"] + extra
+               "--master-port", str(port), os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "1", "--warmup", "1",
+               "--full"] + extra
         out = subprocess.run(cmd, env=env, cwd=root, capture_output=True, text=True, timeout=900)
         assert out.returncode == 0, out.stderr[-3000:]
         lines = [ln for ln in out.stdout.splitlines() if ln.startswith("{")]

@@ -8,7 +8,7 @@ cd /tmp && export TMPDIR=/tmp
 R=$GRAFT_REPO_ROOT
 O=$R/gpurun_out/$TAG
 rm -rf $O; mkdir -p $O
-BENCH="python $R/bench.py --steps 5 --warmup 2 --no-cpu-baseline --no-c5"
+BENCH="python $R/bench.py --steps 5 --warmup 2 --full --no-cpu-baseline --no-c5"
 timeout 200 rocprofv3 --kernel-trace --stats -d $O/prof_bench -o x -- $BENCH > $O/bench_under_rocprof.log 2>&1
 python $R/tools/rocprof_summary.py $(find $O/prof_bench -name "x_results.db" | head -1) > $O/${TAG}_final_kernel_stats.txt
 timeout 900 python $R/tools/kernel_counters.py collect $O/kc > $O/kc_collect.log 2>&1
@@ -30,7 +30,7 @@ timeout 200 python tools/short_probe.py > $O/${TAG}_short_fibres.txt 2>&1
 
 fi
 cd $R
-timeout 400 python bench.py > $O/${TAG}_bench_line.json 2> $O/bench.err
+timeout 400 python bench.py --full > $O/${TAG}_bench_line.json 2> $O/bench.err
 rm -rf $O/prof_*; find $O/kc -name "*.db" -delete
 ls -la $O
 head -12 $O/${TAG}_final_kernel_stats.txt

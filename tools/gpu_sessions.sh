@@ -15,7 +15,7 @@ s1)   # the certifier, the pinned-rung matrix, the pruned kernel: new test files
   timeout 900 python -m pytest tests/test_gpu_certify.py tests/test_gpu_matrix.py -m gpu -x -q > $OUT/pytest_new.log 2>&1; echo "new files: $(tail -1 $OUT/pytest_new.log)" | tee $OUT/summary.txt
   timeout 900 python -m pytest tests -m gpu -x -q --durations=15 > $OUT/pytest_default.log 2>&1; echo "default: $(tail -1 $OUT/pytest_default.log)" | tee -a $OUT/summary.txt
   { python tools/fuzz.py 90 611; python tools/fuzz.py 30 612 nd; python tools/fuzz.py 40 613 long; } > $OUT/fuzz.txt 2>&1; grep "^fuzz\|MISMATCH\|Error" $OUT/fuzz.txt | tee -a $OUT/summary.txt
-  python bench.py --steps 20 --warmup 5 > $OUT/bench.json 2> $OUT/bench.err; python - <<'P' | tee -a $OUT/summary.txt
+  python bench.py --steps 20 --warmup 5 --full > $OUT/bench.json 2> $OUT/bench.err; python - <<'P' | tee -a $OUT/summary.txt
 import json,sys
 d=json.loads(open(sys.argv[1] if len(sys.argv)>1 else 'gpurun_out/r6/s1/bench.json').read().strip().splitlines()[-1])
 print('headline ms', d['ms_per_step'], {k:round(v['avg_launch_ms']*1e3,1) for k,v in d['roofline']['by_kernel'].items()})
@@ -37,7 +37,7 @@ s4)   # the certifier with steps counted above the last-sample slack: new files,
   PROXTV_VERBOSE=1 timeout 900 python -m pytest tests/test_gpu_certify.py tests/test_gpu_matrix.py -m gpu -x -q > $OUT/pytest_new.log 2>&1; echo "new files: $(tail -1 $OUT/pytest_new.log)" | tee $OUT/summary.txt; grep "certify:" $OUT/pytest_new.log | cut -c1-260 | sort | uniq -c | sort -rn | head -20 | tee -a $OUT/summary.txt
   timeout 900 python -m pytest tests -m gpu -x -q --durations=15 > $OUT/pytest_default.log 2>&1; echo "default: $(tail -1 $OUT/pytest_default.log)" | tee -a $OUT/summary.txt
   { PROXTV_VERBOSE=1 python tools/fuzz.py 120 611; python tools/fuzz.py 30 612 nd; PROXTV_VERBOSE=1 python tools/fuzz.py 60 613 long; } > $OUT/fuzz.txt 2>&1; grep "certify:" $OUT/fuzz.txt | cut -c1-260 | head -30 | tee -a $OUT/summary.txt; grep "^fuzz\|MISMATCH\|Error" $OUT/fuzz.txt | tee -a $OUT/summary.txt
-  python bench.py --steps 20 --warmup 5 > $OUT/bench.json 2> $OUT/bench.err; tail -c 600 $OUT/bench.json
+  python bench.py --steps 20 --warmup 5 --full > $OUT/bench.json 2> $OUT/bench.err; tail -c 600 $OUT/bench.json
   ;;
 s5)   # how often is a sweep of the headline marked dirty at all?
   python tools/dirty_rate.py 2>&1 | tee $OUT/dirty_rate.txt
@@ -131,7 +131,7 @@ w1)   # knots known by windows (pin_seed = 2): the pinning tests, A/B by option 
 w2)   # the window stages gated (wave ballots; the policy's half-penalty fraction): tests, A/B by option, the bench line
   timeout 900 python -m pytest tests/test_gpu_pin.py tests/test_gpu_large.py -m gpu -x -q > $OUT/pytest_pin.log 2>&1; echo "pin + large tests: $(tail -1 $OUT/pytest_pin.log)" | tee $OUT/summary.txt
   ab --reps 5 --rounds 2 --cases c2@0.8,c2@1.0,c2@1.5,c2@3,c2@5,c2@10,pd2@1.0,yang2@1.0,s2048@1.0,c4@1.0 base jumps,pin_seed=1 > $OUT/ab_windows.txt 2>&1; cat $OUT/ab_windows.txt
-  python bench.py --steps 10 --warmup 3 > $OUT/bench.json 2> $OUT/bench.err; python - <<'P' | tee -a $OUT/summary.txt
+  python bench.py --steps 10 --warmup 3 --full > $OUT/bench.json 2> $OUT/bench.err; python - <<'P' | tee -a $OUT/summary.txt
 import json
 d=json.loads(open('gpurun_out/r6/w2/bench.json').read().strip().splitlines()[-1])
 print('headline ms', d['ms_per_step'], {k:round(v['avg_launch_ms']*1e3,1) for k,v in d['roofline']['by_kernel'].items()})
@@ -162,7 +162,7 @@ final4)  # window seeds (always on, stages gated wave by wave) + mid-solve sampl
 final5)  # the round's last build: the whole suite, smoke, the two-rank dry run of bench.py on one GPU, soaks, a certified campaign at large penalties
   timeout 1500 python -m pytest tests -m gpu -x -q --durations=6 > $OUT/pytest_default.log 2>&1; echo "default: $(tail -1 $OUT/pytest_default.log)" | tee $OUT/summary.txt
   python -c "import __graft_entry__ as g; g.smoke()" > $OUT/smoke.log 2>&1; tail -1 $OUT/smoke.log | tee -a $OUT/summary.txt
-  PROXTV_BENCH_SHARED_GPU=1 timeout 600 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29517 bench.py --gpus 2 --steps 3 --warmup 1 --no-cpu-baseline > $OUT/bench2.json 2> $OUT/bench2.err; python -c "
+  PROXTV_BENCH_SHARED_GPU=1 timeout 600 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29517 bench.py --gpus 2 --steps 3 --warmup 1 --full --no-cpu-baseline > $OUT/bench2.json 2> $OUT/bench2.err; python -c "
 import json;d=json.loads(open('$OUT/bench2.json').read().strip().splitlines()[-1]);print('2 ranks on one GPU (dry run):',d['n_gpus'],'ranks',round(d['ms_per_step'],2),'ms per step, c5 gather checked',d['c5'].get('gather_checked'))" | tee -a $OUT/summary.txt
   { python tools/fuzz.py 200 681; python tools/fuzz.py 200 682; python tools/fuzz.py 50 683 nd; python tools/fuzz.py 80 684 long; } > $OUT/fuzz.txt 2>&1; grep "^fuzz\|MISMATCH\|Error" $OUT/fuzz.txt | tee -a $OUT/summary.txt
   python tools/certified_campaign.py 200 7 high > $OUT/campaign_7_high.txt 2>&1; tail -1 $OUT/campaign_7_high.txt | tee -a $OUT/summary.txt; grep "certify:" $OUT/campaign_7_high.txt | cut -c1-260 | head -10 | tee -a $OUT/summary.txt
