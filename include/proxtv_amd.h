@@ -240,6 +240,23 @@ int proxtv_tv1_fibres_dev(const double *in, double *out, const int *ns /*host*/,
 long proxtv_certify_fibres_dev(const double *in, const double *out, const int *ns /*host*/, int nds, int dim, double lambda,
                                const double *weights, void *stream);
 
+/* The derivative of that prox, at its output: y is what proxtv_tv1_fibres_dev returned for the same ns / dim (no lambda and no weights
+   are needed).  Edge k of a fibre is a STEP iff |y[k+1] - y[k]| > 256 * 2^-52 * max(|y[k]|, |y[k+1]|) + 4e-10 (the certifier's constants);
+   segments are the maximal runs of samples between steps, and wherever the prox is differentiable its Jacobian P = dy/dx replaces every
+   sample by the mean over its segment.  P is symmetric, so this one call is the VJP and the JVP in x:
+     gx = P g                                      (shape of y; gx may be g itself)
+     gw[k] = sigma_k (gx[k] - gx[k+1])             (gw or NULL: ns[dim] reduced by one, the gradient in the penalty of edge k -- for a uniform
+                                                    lambda, d/dlambda is the sum of gw; sigma_k = +1 / -1 on a step up / down, and gw = 0
+                                                    exactly on an edge that is no step)
+     nseg[j] = segments of fibre j = trace of P    (nseg or NULL: one int per fibre, in the column-major order of the array with `dim`
+                                                    removed; the degrees of freedom SURE asks for)
+   Two limits of the rule: at a kink -- a jump that is zero up to the rule -- the prox is not differentiable and the merged segment is
+   what comes out; and the absolute 4e-10 makes data far below 1e-9 in magnitude one segment per fibre.  ns[dim] == 1: gx = g, nothing is
+   written to gw.  gx == NULL (g may then be NULL too): only nseg is computed, in one pass over y.  No atomics: the same call gives the
+   same bits.  Synchronises the stream; returns 1, or 0 with proxtv_last_error set. */
+int proxtv_tv1_fibres_vjp_dev(const double *y, const double *g, double *gx /*or NULL*/, double *gw /*or NULL*/, int *nseg /*or NULL*/,
+                              const int *ns /*host*/, int nds, int dim, void *stream);
+
 /* Batch of B independent MxN images stored back to back (image b at unary + b*M*N), each solved
    with DR2_TV semantics (oracle = loop of DR2_TV).  All B images advance together, one
    launch per sweep over B*N (columns) / B*M (rows) fibres. */

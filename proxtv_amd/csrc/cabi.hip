@@ -659,6 +659,27 @@ long proxtv_certify_fibres_dev(const double *in, const double *out, const int *n
     return failed;
 }
 
+int proxtv_tv1_fibres_vjp_dev(const double *y, const double *g, double *gx, double *gw, int *nseg, const int *ns, int nds, int dim,
+                              void *stream) {
+    return guarded("proxtv_tv1_fibres_vjp_dev", nullptr, 1, [&] {
+        if (dim < 0 || dim >= nds) reject("dimension out of range");
+        hipStream_t st = pick(stream);
+        if (!gx) {   // the segment counts alone
+            tv1_fibres_vjp(y, g, nullptr, nullptr, nseg, ns, nds, dim, st);
+            return;
+        }
+        if (!g) reject("g is required when gx is asked for");
+        const size_t n = (size_t)total(ns, nds), nw = (gw && ns[dim] > 1) ? n / (size_t)ns[dim] * (size_t)(ns[dim] - 1) : 0;
+        // gx == g is served in place (vjp.hip); any other overlap goes through scratch like everywhere else
+        OutGuard ox(gx, n, {{y, n}, {gx == g ? nullptr : g, n}, {gw, nw}});
+        OutGuard ow(nw ? gw : nullptr, nw, {{y, n}, {g, n}});
+        tv1_fibres_vjp(y, g, ox.ptr(), ow.ptr(), nseg, ns, nds, dim, st);
+        ox.commit(st);
+        ow.commit(st);
+        PTV_HIP(hipStreamSynchronize(st));
+    });
+}
+
 int proxtv_tvp_fibres_dev(const double *in, double *out, const int *ns, int nds, int dim, double lambda, double p,
                           void *stream) {
     return guarded("proxtv_tvp_fibres_dev", nullptr, 1, [&] {

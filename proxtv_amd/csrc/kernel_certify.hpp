@@ -2,6 +2,8 @@
 // (One of the pieces of sweep_kernels.hpp, which includes them in order; not meant to be included on its own.)
 #pragma once
 
+#include "certify_rule.hpp"   // kCertifyTol, kCertifyStep, kCertifyUlp, kCertifySlack
+
 namespace ptv {
 namespace swp {
 
@@ -19,8 +21,7 @@ namespace swp {
 // kernels) do the same, bit for bit.  kCertifySlack = 4 EPSILON is allowed for it: a wrong sample below ~1e-9 is inside what the
 // reference's own solvers disagree by among themselves.  A fibre that fails is flagged; the host re-solves the flagged fibres with the sequential walk
 // (sweep_seq_kernel through its fibre gate) and counts them.  Fibres with a negative penalty are not checked (the reference's behaviour
-// there is its code, not a minimisation).
-constexpr double kCertifyTol = 64.0, kCertifyStep = 256.0, kCertifyUlp = 2.220446049250313e-16, kCertifySlack = 4.0 * kEps;
+// there is its code, not a minimisation).  (The four constants: certify_rule.hpp.)
 
 struct CertifyAcc {
     double u = 0.0, scale = 0.0, viol = 0.0;

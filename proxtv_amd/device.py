@@ -208,3 +208,65 @@ def certify_fibres(x, y, w, dim, weights=None):
     if failed == -2:
         _lib.check("device.certify_fibres")
     return int(failed)
+
+
+def _counts_empty(shape, dim, device):
+    """int32 tensor with the shape of an array without its dimension `dim`, column-major (0-d for a 1-D array)."""
+    rest = tuple(s for i, s in enumerate(shape) if i != dim)
+    if not rest:
+        return torch.empty((), device=device, dtype=torch.int32)
+    return colmajor_empty(rest, device=device, dtype=torch.int32)
+
+
+def tv1_fibres_vjp(y, g, dim, need_gw=False, need_nseg=False, out=None):
+    """The derivative of ``y = tv1_fibres(x, w, dim[, weights])`` applied to `g`: returns (gx, gw | None, nseg | None).
+
+    gx = P g, where P = dy/dx replaces every sample by the mean over its segment of `y` (the runs between the steps of `y` along
+    `dim`; step rule and its limits: include/proxtv_amd.h) -- P is symmetric, so this is the VJP and the JVP in x.  gw (`need_gw`) is
+    the gradient in the per-edge penalties, shaped like `weights`; for a uniform penalty d/dw is ``gw.sum()``.  nseg (`need_nseg`) holds
+    the segments of every fibre (int32, the shape of `y` without `dim`): trace P, the degrees of freedom.  Only `y` is needed, neither
+    x nor the penalties.  A `g` in another layout is copied; `out` may be `g`."""
+    _check(y, "y")
+    if not 0 <= int(dim) < y.dim():
+        raise ValueError(f"dim {dim} out of range for a {y.dim()}-D array")
+    dim = int(dim)
+    if not (isinstance(g, torch.Tensor) and g.is_cuda and g.dtype == torch.float64):
+        raise ValueError("g: expected a float64 CUDA tensor")
+    if g.device != y.device:
+        raise ValueError(f"g: lives on {g.device}, the input on {y.device}")
+    if tuple(g.shape) != tuple(y.shape):
+        raise ValueError(f"g: shape {tuple(g.shape)}, expected {tuple(y.shape)}")
+    if not _is_colmajor(g):
+        g = to_colmajor(g)
+    gx = _out(out, y)
+    ns = np.array(y.shape, dtype=np.int32)
+    gw = nseg = None
+    if need_gw:
+        wshape = list(y.shape)
+        wshape[dim] -= 1
+        gw = colmajor_empty(wshape, device=y.device)
+    if need_nseg:
+        nseg = _counts_empty(y.shape, dim, y.device)
+    with torch.cuda.device(y.device):
+        lib = _lib.require_device()
+        lib.proxtv_tv1_fibres_vjp_dev(y.data_ptr(), g.data_ptr(), gx.data_ptr(), gw.data_ptr() if need_gw and gw.numel() else 0,
+                                      nseg.data_ptr() if need_nseg and nseg.numel() else 0, ns.ctypes.data, y.dim(), dim,
+                                      _stream(y.device))
+    _lib.check("device.tv1_fibres_vjp")
+    return gx, gw, nseg
+
+
+def tv1_fibres_dof(y, dim):
+    """Segments of every fibre of ``y = tv1_fibres(x, w, dim)`` along `dim` (int32, the shape of `y` without `dim`): the trace of the
+    prox's Jacobian, i.e. the degrees of freedom SURE needs.  One pass over `y`; nothing else is computed."""
+    _check(y, "y")
+    if not 0 <= int(dim) < y.dim():
+        raise ValueError(f"dim {dim} out of range for a {y.dim()}-D array")
+    ns = np.array(y.shape, dtype=np.int32)
+    nseg = _counts_empty(y.shape, int(dim), y.device)
+    with torch.cuda.device(y.device):
+        lib = _lib.require_device()
+        lib.proxtv_tv1_fibres_vjp_dev(y.data_ptr(), 0, 0, 0, nseg.data_ptr() if nseg.numel() else 0, ns.ctypes.data, y.dim(), int(dim),
+                                      _stream(y.device))
+    _lib.check("device.tv1_fibres_dof")
+    return nseg
