@@ -257,6 +257,27 @@ long proxtv_certify_fibres_dev(const double *in, const double *out, const int *n
 int proxtv_tv1_fibres_vjp_dev(const double *y, const double *g, double *gx /*or NULL*/, double *gw /*or NULL*/, int *nseg /*or NULL*/,
                               const int *ns /*host*/, int nds, int dim, void *stream);
 
+/* The derivative of the 2-D Douglas-Rachford solves (DR2_TV / DR2L1W_TV / the batch), on B images stored back to back: for the cotangent
+   g of the result,
+     gU          the gradient in `unary`                                    (M x N per image; gU may be g itself)
+     gW1, gW2    the gradients in the per-edge penalties, or NULL           ((M-1) x N and M x (N-1) per image: the shapes of W1m / W2m.  Also
+                                                                             with uniform W1 / W2, where they hold the per-edge terms)
+     glam        HOST double[2 B] or NULL: (sum gW1, sum gW2) per image     (the gradients in uniform W1 / W2)
+     s           the forward result, or NULL
+   W1m and W2m both given: the weighted solve (W1, W2 are ignored); both NULL: the uniform one.  The call is self-contained: it runs the
+   UNFUSED forward recurrence (t0 = 2 mean(U); x1 = prox_cols(t), x2 = prox_rows(U - t + 2 x1), t <- t - x1 + x2; a final pair of sweeps),
+   keeping the 2 (maxit + 1) sweep outputs in pool scratch -- 2 (maxit + 1) * 8 * M * N * B bytes; beyond the pool's cap
+   (PROXTV_POOL_CAP_MB) the call is refused and proxtv_last_error names the bytes -- and then applies proxtv_tv1_fibres_vjp_dev's segmented
+   means sweep by sweep, last sweep first, with the pointwise work of the recurrence inside those kernels.  What comes out is the
+   derivative of that recurrence: its forward agrees with proxtv_DR2_TV_dev's fused sweeps to rounding, not bit for bit.  The step rule and
+   its two limits (kinks; the absolute 4e-10) are proxtv_tv1_fibres_vjp_dev's.  maxit <= 0: 35.  M*N*B == 0: returns 1, nothing is written.
+   M == 1 or N == 1 is fine.  No array may overlap another, except gU == g; exactly one weight map, a missing unary / g / gU, an overlap or
+   a tape beyond the cap: returns 0 with proxtv_last_error set and nothing written.  No atomics: the same call gives the same bits, and an
+   image of a batch the bits of its own call.  Synchronises the stream; returns 1 on success. */
+int proxtv_DR2_TV_vjp_dev(size_t M, size_t N, size_t B, const double *unary, double W1, double W2, const double *W1m /*or NULL*/,
+                          const double *W2m /*or NULL*/, const double *g, double *s /*or NULL*/, double *gU, double *gW1 /*or NULL*/,
+                          double *gW2 /*or NULL*/, double *glam /*host, or NULL*/, int maxit, void *stream);
+
 /* Batch of B independent MxN images stored back to back (image b at unary + b*M*N), each solved
    with DR2_TV semantics (oracle = loop of DR2_TV).  All B images advance together, one
    launch per sweep over B*N (columns) / B*M (rows) fibres. */

@@ -680,6 +680,42 @@ int proxtv_tv1_fibres_vjp_dev(const double *y, const double *g, double *gx, doub
     });
 }
 
+int proxtv_DR2_TV_vjp_dev(size_t M, size_t N, size_t B, const double *unary, double W1, double W2, const double *W1m, const double *W2m,
+                          const double *g, double *s, double *gU, double *gW1, double *gW2, double *glam, int maxit, void *stream) {
+    return guarded("proxtv_DR2_TV_vjp_dev", nullptr, 1, [&] {
+        const size_t n = M * N * B;
+        if (n == 0) return;
+        if (M > 0x7fffffffu || N > 0x7fffffffu || B > 65535u) reject("image extents beyond 2^31 - 1 or more than 65535 images");
+        if (!unary || !g || !gU) reject("unary, g and gU are required");
+        if ((W1m != nullptr) != (W2m != nullptr)) reject("weight maps come in pairs: W1m and W2m, or neither");
+        // every array is read or written while others are: none may overlap another, except that gU may BE g (vjp.hip)
+        const size_t nw1 = (M - 1) * N * B, nw2 = M * (N - 1) * B;
+        struct Span { const double *p; size_t n; bool out; const char *name; };
+        const Span spans[] = {{unary, n, false, "unary"}, {W1m, nw1, false, "W1m"}, {W2m, nw2, false, "W2m"}, {g, n, false, "g"},
+                              {s, n, true, "s"}, {gU, n, true, "gU"}, {gW1, nw1, true, "gW1"}, {gW2, nw2, true, "gW2"}};
+        for (const Span &o : spans) {
+            if (!o.out || !o.p || !o.n) continue;
+            for (const Span &i : spans) {
+                if (&i == &o || !i.p || !i.n || (&o == &spans[5] && &i == &spans[3] && gU == g)) continue;
+                if (i.out && &i > &o) continue;   // (a pair of outputs: once)
+                if (i.p < o.p + o.n && o.p < i.p + i.n) {
+                    set_error("%s overlaps %s (only gU may alias g, and then exactly)", o.name, i.name);
+                    throw HipFailure{hipErrorInvalidValue};
+                }
+            }
+        }
+        const size_t tape = dr2_vjp_tape_bytes(M, N, B, maxit);
+        if (tape > pool_cap_bytes()) {
+            set_error("the tape of sweep outputs needs %zu bytes, the scratch pool is capped at %zu (PROXTV_POOL_CAP_MB)", tape, pool_cap_bytes());
+            throw HipFailure{hipErrorOutOfMemory};
+        }
+        hipStream_t st = pick(stream);
+        SolveScope scope(st);
+        dr2_vjp(M, N, B, unary, W1, W2, W1m, W2m, g, s, gU, gW1, gW2, glam, maxit, st);
+        scope.finish();
+    });
+}
+
 int proxtv_tvp_fibres_dev(const double *in, double *out, const int *ns, int nds, int dim, double lambda, double p,
                           void *stream) {
     return guarded("proxtv_tvp_fibres_dev", nullptr, 1, [&] {

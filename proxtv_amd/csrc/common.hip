@@ -174,7 +174,7 @@ struct ThreadStates {
 };
 static thread_local ThreadStates g_ts;
 
-static size_t pool_cap_bytes() {
+size_t pool_cap_bytes() {
     static const size_t cap = [] {
         const char *e = getenv("PROXTV_POOL_CAP_MB");
         return (size_t)(e ? atol(e) : 65536) << 20;   // 64 GiB of 288: a 64 x 2048^2 batch solve keeps ~11 GiB

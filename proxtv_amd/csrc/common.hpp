@@ -127,6 +127,7 @@ class Scratch {
     int dev_ = 0;   // device the block lives on (it returns to that device's pool)
 };
 void release_scratch();
+size_t pool_cap_bytes();   // what the pool keeps cached at most (PROXTV_POOL_CAP_MB); calls that size their scratch by an argument refuse beyond it
 
 // ---- fibre geometry ---------------------------------------------------------------------------------------------
 // Fibres of an N-D column-major array along one dimension (reference addressing: src/TV2Dopt.cpp:140-145,184):

@@ -24,6 +24,13 @@ long certify_fibres(const double *in, const double *out, const int *ns, int nds,
 void tv1_fibres_vjp(const double *y, const double *g, double *gx, double *gw, int *nseg, const int *ns, int nds, int dim,
                     hipStream_t s);
 
+// the derivative of dr2 (vjp.hip): runs the unfused recurrence with its 2 (maxit + 1) sweep outputs kept in pool scratch
+// (dr2_vjp_tape_bytes; the caller checks it against pool_cap_bytes), then the reverse sweeps.  out / gW1 / gW2 / glam may be null; gU may
+// be g, no other overlap.  glam: HOST double[2 B], (sum gW1, sum gW2) per image.  Returns with the stream drained.
+size_t dr2_vjp_tape_bytes(size_t M, size_t N, size_t B, int maxit);
+void dr2_vjp(size_t M, size_t N, size_t B, const double *unary, double W1, double W2, const double *W1m, const double *W2m, const double *g,
+             double *out, double *gU, double *gW1, double *gW2, double *glam, int maxit, hipStream_t s);
+
 // out = prox along `dim` with the TV-L1 (norm 1: the sweep kernels) or TV-L2 (norm 2: tv2.hip) penalty; in != out
 void prox_fibres(const double *in, double *out, const int *ns, int nds, int dim, double lam, double norm, hipStream_t s);
 

@@ -256,6 +256,59 @@ def tv1_fibres_vjp(y, g, dim, need_gw=False, need_nseg=False, out=None):
     return gx, gw, nseg
 
 
+def dr2_vjp(x, g, w_col, w_row=None, max_iters=0, weights_col=None, weights_row=None, need_gw=False, need_y=False):
+    """The derivative of the Douglas-Rachford solves ``tv1_2d(x, w_col, w_row=w_row)`` / ``tv1w_2d(x, weights_col, weights_row)`` /
+    ``tv1_2d_batch`` applied to the cotangent `g` of their result: returns (gx, gw_col, gw_row, glam, y).
+
+    `x` and `g` are (M, N), or (M, N, B) for a batch of independent images.  gx is the gradient in x.  With `need_gw`, gw_col / gw_row are
+    the gradients in the per-edge penalties (the shapes of `weights_col` / `weights_row`, also for a uniform penalty) and glam, a numpy
+    array of shape (2,) or (B, 2), their sums per image: the gradients in a uniform (w_col, w_row).  ``need_gw="sums"`` returns glam
+    alone.  y (`need_y`) is the forward result of the call's own, unfused recurrence: device.tv1_2d's up to rounding.  One call:
+    proxtv_DR2_TV_vjp_dev (include/proxtv_amd.h), which keeps 2 (max_iters + 1) arrays of x's size in pool scratch while it runs.  A `g`
+    in another layout is copied."""
+    _check(x, "x")
+    if x.dim() not in (2, 3):
+        raise ValueError(f"x: expected an (M, N) image or an (M, N, B) batch, got {x.dim()} dimensions")
+    if not (isinstance(g, torch.Tensor) and g.is_cuda and g.dtype == torch.float64):
+        raise ValueError("g: expected a float64 CUDA tensor")
+    if g.device != x.device:
+        raise ValueError(f"g: lives on {g.device}, the input on {x.device}")
+    if tuple(g.shape) != tuple(x.shape):
+        raise ValueError(f"g: shape {tuple(g.shape)}, expected {tuple(x.shape)}")
+    if not _is_colmajor(g):
+        g = to_colmajor(g)
+    if (weights_col is None) != (weights_row is None):
+        raise ValueError("weights_col and weights_row come in pairs")
+    M, N = x.shape[:2]
+    B = x.shape[2] if x.dim() == 3 else 1
+    tail = tuple(x.shape[2:])
+    shape_col, shape_row = (max(M - 1, 0), N) + tail, (M, max(N - 1, 0)) + tail
+    if weights_col is not None:
+        _check(weights_col, "weights_col", like=x, shape=shape_col)
+        _check(weights_row, "weights_row", like=x, shape=shape_row)
+    w_row = w_col if w_row is None else w_row
+    gx = colmajor_empty(x.shape, device=x.device)
+    y = colmajor_empty(x.shape, device=x.device) if need_y else None
+    gw_col = gw_row = glam = None
+    if need_gw:
+        glam = np.zeros((B, 2))
+        if need_gw != "sums":
+            gw_col = colmajor_empty(shape_col, device=x.device)
+            gw_row = colmajor_empty(shape_row, device=x.device)
+    ptr = lambda t: t.data_ptr() if t is not None and t.numel() else 0   # noqa: E731
+    # (a weight map without edges -- M == 1 or N == 1 -- has no storage: any non-null address says "weighted", nothing is read through it)
+    wptr = lambda t: 0 if t is None else (ptr(t) or x.data_ptr())        # noqa: E731
+    with torch.cuda.device(x.device):
+        lib = _lib.require_device()
+        lib.proxtv_DR2_TV_vjp_dev(M, N, B, ptr(x), float(w_col), float(w_row), wptr(weights_col), wptr(weights_row), ptr(g),
+                                  ptr(y), ptr(gx), ptr(gw_col), ptr(gw_row), glam.ctypes.data if need_gw else 0, int(max_iters),
+                                  _stream(x.device))
+    _lib.check("device.dr2_vjp")
+    if glam is not None and x.dim() == 2:
+        glam = glam[0]
+    return gx, gw_col, gw_row, glam, y
+
+
 def tv1_fibres_dof(y, dim):
     """Segments of every fibre of ``y = tv1_fibres(x, w, dim)`` along `dim` (int32, the shape of `y` without `dim`): the trace of the
     prox's Jacobian, i.e. the degrees of freedom SURE needs.  One pass over `y`; nothing else is computed."""
