@@ -223,6 +223,9 @@ struct NoFar {
 // between the two passes, so the forward pass costs a row one LDS read, the backward pass none, and ops whose output needs the row's
 // own sample (DR_COL) take the same array-free passes as the others instead of a dynamic back-fill loop per piece.  Same arithmetic
 // in the same order as the general form: bit-identical (tests/host_harness.cpp runs all three).
+// FULL == 3: the register form for the segment that holds the fibre's last sample -- every lane of the wave takes it, a lane's chunk
+// may be partial (ce - cs < C: the fibre's last chunk; rows from ce on are neither summed nor written) and the knot behind the fibre's
+// last sample has height 0 as in the general form.  Bit-identical to it as well (tests/along_tail_harness.cpp).
 // The rows BEFORE a lane's chunk that belong to the first piece ending in it: their sum and count.  rebuild_owned reads them itself where
 // nothing can have replaced them yet (lanes of one wave, in lockstep); where the lanes of a fibre sit in different waves (the strided
 // tiles) an UNPROVEN lane's rows before its chunk may be somebody else's to write -- the two walks disagree, that is what unproven
@@ -359,13 +362,16 @@ __device__ __forceinline__ void rebuild_owned(Win &win, const ChunkRec &rec, int
                 return over(num);
             }
         };
+        constexpr bool PART = FULL == 3;
+        const int nrow = ce - cs;
 #pragma unroll
         for (int u = 0; u < C; u++) {
-            const double yu = slot[u];
+            const bool in = !PART || u < nrow;
+            const double yu = in ? slot[u] : 0.0;
             s += yu;
             n += 1;
-            if ((rec.ends >> u) & 1u) {
-                const double hk = height(u);
+            if (in && ((rec.ends >> u) & 1u)) {
+                const double hk = (PART && u == uend) ? 0.0 : height(u);
                 const double v = over_n(s + (hk - hprev), n);
                 win.put(cs + u, F::fuse(yu, v));
                 slot[u] = v;
@@ -377,8 +383,8 @@ __device__ __forceinline__ void rebuild_owned(Win &win, const ChunkRec &rec, int
         have = tail_value(s, (double)n, hprev, cur);
 #pragma unroll
         for (int u = C - 1; u >= 0; u--) {
-            const bool e = (rec.ends >> u) & 1u;
-            if (have && !e) win.put(cs + u, F::fuse(slot[u], cur));
+            const bool e = ((rec.ends >> u) & 1u) && (!PART || u < nrow);
+            if (have && !e && (!PART || u < nrow)) win.put(cs + u, F::fuse(slot[u], cur));
             cur = e ? slot[u] : cur;
             have = have || e;
         }

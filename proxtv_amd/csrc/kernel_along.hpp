@@ -131,10 +131,17 @@ __global__ __launch_bounds__(64 * kAlongWaves) void sweep_along_kernel(SweepArgs
     // immediate (the first segment's zone rows, which nothing ever reads, take copies of sample 0: a clamped address instead of a mask).
     // Uniform over the wave for whole-wave segments (G = 64: fibre and segment are scalar values there).
     const bool interior = G == 64 && !ONESEG && live && seg_s + SEG + T <= len - 1;
+    // `endseg`: the segment that holds the fibre's last sample.  Its shape is known from scalars too (len, seg_s), so it takes the same
+    // forms with the fibre's end in the place of a mask: staged rows past the last sample take copies of the last sample (nothing ever
+    // reads them: every walk and every sum stops at len), the rebuild keeps the chunks in registers with a row count per lane (only the
+    // fibre's last chunk is partial), and the whole groups of 64 rows stream out untested.
+    const bool endseg = G == 64 && !ONESEG && live && !interior && seg_s < len && seg_s + SEG >= len;
     const unsigned ul = (unsigned)gl;
-    auto stage_interior = [&]() {
+    auto stage_interior = [&](auto tailc) {
+        constexpr bool TC = decltype(tailc)::value;   // endseg: rows are clamped to the window's last row
         constexpr int NB = NU <= 20 ? NU : (NU + 1) / 2;
         const long row0 = fbase + lo, wrow0 = wbase + lo;   // (scalar; the first segment: lo = -HZ, element 0 is clamped below)
+        const unsigned rlast = (unsigned)(len - 1 - lo), wlast = (unsigned)max(len - 2 - lo, 0);   // (scalar)
 #pragma unroll
         for (int b0 = 0; b0 < NU; b0 += NB) {
             double s0[NB], s1[NB], sw[WEIGHTED ? NB : 1];
@@ -144,10 +151,14 @@ __global__ __launch_bounds__(64 * kAlongWaves) void sweep_along_kernel(SweepArgs
                 s0[u] = s1[u] = 0.0;
                 if (b0 + u >= NU) continue;
                 long idx = (row0 + rel) + (long)ul, widx = (wrow0 + rel) + (long)ul;
+                if (TC) {   // (a 32-bit minimum per row; the base stays scalar)
+                    idx = row0 + (long)min((unsigned)rel + ul, rlast);
+                    widx = wrow0 + (long)min((unsigned)rel + ul, wlast);
+                }
                 if (rel < HZ) {   // (compile time: the element that holds the zone rows)
-                    const int r = max(lo + rel + gl, 0);
+                    const int r = TC ? min(max(lo + rel + gl, 0), len - 1) : max(lo + rel + gl, 0);
                     idx = fbase + r;
-                    widx = wbase + r;
+                    widx = wbase + (TC ? min(r, max(len - 2, 0)) : r);
                 }
                 if (rel + G <= ROWS) {
                     Op<OP>::fetch_in(p, idx, s0[u], s1[u]);
@@ -156,6 +167,8 @@ __global__ __launch_bounds__(64 * kAlongWaves) void sweep_along_kernel(SweepArgs
                     Op<OP>::fetch_in(p, idx, s0[u], s1[u]);
                     if (WEIGHTED) sw[WEIGHTED ? u : 0] = p.w[widx];
                 }
+                // (the penalty of the edge behind the fibre's last sample is 0, as the general form stages it)
+                if (TC && WEIGHTED && (unsigned)rel + ul >= rlast) sw[WEIGHTED ? u : 0] = 0.0;
             }
 #pragma unroll
             for (int u = 0; u < NB; u++) {
@@ -169,7 +182,10 @@ __global__ __launch_bounds__(64 * kAlongWaves) void sweep_along_kernel(SweepArgs
         }
     };
     if (interior && !(plan.ablate & 4)) {
-        stage_interior();
+        stage_interior(std::false_type{});
+    } else
+    if (endseg && !(plan.ablate & 4)) {
+        stage_interior(std::true_type{});
     } else
     if (live && !(plan.ablate & 4)) {
         // every load of a batch is issued before the first is waited for; NB rows per lane and batch (the 31-sample chunks stage
@@ -468,7 +484,11 @@ __global__ __launch_bounds__(64 * kAlongWaves) void sweep_along_kernel(SweepArgs
     if (!WEIGHTED && interior && !(plan.ablate & 1))   // (every lane of the wave holds a whole chunk: the form that keeps it in registers)
         rebuild_owned<Op<OP>, WEIGHTED, C, PTV_ALONG_UNROLL, TAB, lds_double *, (ROBUST ? TS : 0), 2>(win, rec, cs, ce, len, start, !bad, wlo, gl == G - 1, p.lam,
                                                                                       (lds_double *)rtab, nullptr, plan.legacy != 0);
-    else if (has_chunk && !(plan.ablate & 1))
+    else if (!WEIGHTED && endseg && !(plan.ablate & 1)) {   // (the same form with a row count: the fibre's last chunk may be partial; lanes past it idle)
+        if (has_chunk)
+            rebuild_owned<Op<OP>, WEIGHTED, C, PTV_ALONG_UNROLL, TAB, lds_double *, (ROBUST ? TS : 0), 3>(win, rec, cs, ce, len, start, !bad, wlo, gl == G - 1 || ce == len, p.lam,
+                                                                                          (lds_double *)rtab, nullptr, plan.legacy != 0);
+    } else if (has_chunk && !(plan.ablate & 1))
         rebuild_owned<Op<OP>, WEIGHTED, C, PTV_ALONG_UNROLL, TAB, lds_double *, (ROBUST ? TS : 0)>(win, rec, cs, ce, len, start, !bad, wlo, gl == G - 1 || ce == len, p.lam,
                                                                                 (lds_double *)rtab, nullptr, plan.legacy != 0);
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
@@ -491,6 +511,34 @@ __global__ __launch_bounds__(64 * kAlongWaves) void sweep_along_kernel(SweepArgs
                 const double v = Yp[HZ + G * (t0 + u) + ul];
                 if (Op<OP>::FUSED) Op<OP>::store_fused(p, idx, v);
                 else               Op<OP>::finish(p, idx, ex[u], v);
+            }
+        }
+    } else
+    if (endseg && !(plan.ablate & 2)) {   // (the same for the whole groups of 64 rows -- a scalar count -- and one tested group for the rest)
+        const long out0 = fbase + seg_s;
+        const int nfull = (seg_e - seg_s) / G;
+        const bool rest = gl < (seg_e - seg_s) - nfull * G;
+#pragma unroll
+        for (int t0 = 0; t0 < C; t0 += UL) {
+            if (t0 > nfull) break;
+            Ext ex[UL];
+#pragma unroll
+            for (int u = 0; u < UL; u++) {
+                ex[u] = Ext{0, 0};
+                if (t0 + u >= C || Op<OP>::FUSED) continue;
+                const long idx = (out0 + G * (t0 + u)) + (long)ul;
+                if (t0 + u < nfull) ex[u] = Op<OP>::fetch(p, idx);
+                else if (t0 + u == nfull && rest) ex[u] = Op<OP>::fetch(p, idx);
+            }
+#pragma unroll
+            for (int u = 0; u < UL; u++) {
+                if (t0 + u >= C) continue;
+                const long idx = (out0 + G * (t0 + u)) + (long)ul;
+                if (t0 + u < nfull || (t0 + u == nfull && rest)) {
+                    const double v = Yp[HZ + G * (t0 + u) + ul];
+                    if (Op<OP>::FUSED) Op<OP>::store_fused(p, idx, v);
+                    else               Op<OP>::finish(p, idx, ex[u], v);
+                }
             }
         }
     } else
