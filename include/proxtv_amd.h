@@ -278,6 +278,28 @@ int proxtv_DR2_TV_vjp_dev(size_t M, size_t N, size_t B, const double *unary, dou
                           const double *W2m /*or NULL*/, const double *g, double *s /*or NULL*/, double *gU, double *gW1 /*or NULL*/,
                           double *gW2 /*or NULL*/, double *glam /*host, or NULL*/, int maxit, void *stream);
 
+/* The derivative of the two Dykstra loops tvgen dispatches to, with TV-L1 terms on an N-D array: which = 0, proxtv_PD2_TV_dev (one or two
+   terms); which = 1, proxtv_PD_TV_dev (any number of terms, several may share a dimension).  For the cotangent g of the result,
+     gy          the gradient in y                                          (shape of y; gy may be g itself)
+     glam        HOST double[npen] or NULL: the gradient in `lambdas` AS PASSED -- for which = 1 those are the npen-scaled values the
+                 forward entry point takes, so the gradient in the user's penalties is npen times this
+     x           the forward result, or NULL
+   `iters` is an INPUT: the iteration count the forward solve reported in info[0].  The call is self-contained: it runs exactly `iters`
+   iterations of the UNFUSED recurrence -- it tests no stopping value and reads nothing back -- keeping every sweep output in pool scratch
+   (which = 1: npen * iters arrays of y's size; which = 0: 2 * iters, or one for a single term, where every iteration repeats the first;
+   beyond the pool's cap, PROXTV_POOL_CAP_MB, the call is refused and proxtv_last_error names the bytes), and then applies
+   proxtv_tv1_fibres_vjp_dev's segmented means sweep by sweep, last iteration first, with the pointwise work of the reverse recurrence
+   inside those kernels.  What comes out is the derivative of the `iters`-step recurrence.  Limits: the dependence of the iteration count
+   on the data through the stopping rule is NOT differentiated; the step rule and its two limits (kinks; the absolute 4e-10) are
+   proxtv_tv1_fibres_vjp_dev's; the forward agrees with the fused solve to rounding, not bit for bit.  Per-edge weight maps and TV-L2 terms
+   are not covered (there is no `norms` argument).  A total size of 0: returns 1, nothing is written.  iters < 1, which = 0 with npen > 2,
+   a dimension out of range, a missing y / g / gy, any overlap except gy == g, or a tape beyond the cap: returns 0 with proxtv_last_error
+   set and nothing written.  No atomics: the same call gives the same bits.  Synchronises the stream; returns 1 on success. */
+int proxtv_PD_TV_vjp_dev(int which /*0: PD2_TV, 1: PD_TV*/, const double *y, const double *lambdas /*host, as the forward takes them*/,
+                         const double *dims /*host, 1-based*/, const int *ns /*host*/, int nds, int npen, int iters, const double *g,
+                         double *x /*forward result, or NULL*/, double *gy /*may be g*/, double *glam /*host double[npen], or NULL*/,
+                         void *stream);
+
 /* Batch of B independent MxN images stored back to back (image b at unary + b*M*N), each solved
    with DR2_TV semantics (oracle = loop of DR2_TV).  All B images advance together, one
    launch per sweep over B*N (columns) / B*M (rows) fibres. */

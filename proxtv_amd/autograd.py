@@ -10,7 +10,11 @@ tv1_fibres: forward is device.tv1_fibres; backward is ONE device.tv1_fibres_vjp 
 include/proxtv_amd.h for the step rule and where the prox is not differentiable) plus, for a scalar w, a sum.  The 2-D Douglas-Rachford
 solves are differentiated as loops, natively: forward is the fused device.tv1_2d / tv1w_2d / tv1_2d_batch, only x and the penalties are
 saved, and backward is ONE device.dr2_vjp call, which replays the recurrence on the device and sweeps it in reverse.  The
-other 2-D / N-D solvers (PD, Yang, ...) are not differentiated: compose them from tv1_fibres and torch's pointwise operations.
+N-D entry tvgen is differentiated the same way through its two Dykstra loops ('pd2' / 'pd'): forward is the fused device.tvgen, backward
+ONE device.tvgen_vjp call with the iteration count the forward reported.  The other solvers (PDR, Yang, ...) are not
+differentiated: compose them from tv1_fibres and torch's pointwise operations.
+
+    y = autograd.tvgen(x, [w0, w1, w2], [1, 2, 3])   # a volume; every w a float or a 0-d float64 tensor
 """
 import torch
 
@@ -128,3 +132,49 @@ def tv1_2d_batch(xs, w, max_iters=0):
     if not _wants(xs, w):
         return device.tv1_2d_batch(xs, float(w), max_iters)[0]
     return _DR2.apply(xs, w, w, int(max_iters), False)
+
+
+class _TVGen(torch.autograd.Function):
+    """x, then the penalties one by one (0-d tensors / floats); ds, max_iters and method ride in `spec`."""
+
+    @staticmethod
+    def forward(ctx, x, spec, *ws):
+        ds, max_iters, method = spec
+        xd = _colmajor(x.detach())
+        lams = [float(w) for w in ws]
+        y, info = device.tvgen(xd, lams, ds, max_iters, method)
+        ctx.save_for_backward(xd)
+        ctx.lams, ctx.ds, ctx.method = lams, ds, method
+        ctx.iters = int(info[0])
+        ctx.lam_devices = tuple(w.device if isinstance(w, torch.Tensor) else None for w in ws)
+        return y
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, gy):
+        (x,) = ctx.saved_tensors
+        need_x, need_ws = ctx.needs_input_grad[0], ctx.needs_input_grad[2:]
+        if x.numel() == 0 or ctx.iters < 1:      # (nothing was iterated: the result does not depend on anything)
+            gx, glam = torch.zeros_like(x), [0.0] * len(ctx.lams)
+        else:
+            gx, glam, _ = device.tvgen_vjp(x, gy, ctx.lams, ctx.ds, ctx.iters, ctx.method, need_glam=any(need_ws))
+        gws = tuple(torch.tensor(float(glam[i]), dtype=torch.float64, device=ctx.lam_devices[i]) if need else None
+                    for i, need in enumerate(need_ws))
+        return ((gx if need_x else None), None) + gws
+
+
+def tvgen(x, ws, ds, max_iters=0, method=None):
+    """``device.tvgen(x, ws, ds, max_iters, method)[0]`` with a graph behind it: differentiable in x and in every entry of `ws` that is a
+    0-d float64 tensor (its gradient comes back on that tensor's device; a tensor that appears in several entries receives the sum).
+    method: None (tvgen's dispatch), 'pd2' or 'pd'; 'pdr' and 'yang' raise NotImplementedError when a gradient is asked for.  The result
+    is bit for bit device.tvgen's; when nothing asks for a gradient this IS device.tvgen.  Backward differentiates the iterations the
+    forward ran (its info[0]), not the dependence of their number on the data."""
+    ws = list(ws)
+    for i, w in enumerate(ws):
+        _scalar_penalty(w, f"ws[{i}]")
+    if not _wants(x, *ws):
+        return device.tvgen(x, [float(w) for w in ws], ds, max_iters, method)[0]
+    m = method if method is not None else ("pd2" if len(ws) == 2 else "pd")
+    if m not in ("pd2", "pd"):
+        raise NotImplementedError(f"method {m!r} has no derivative (autograd.tvgen covers 'pd2' and 'pd')")
+    return _TVGen.apply(x, (tuple(float(d) for d in ds), int(max_iters), method), *ws)

@@ -716,6 +716,43 @@ int proxtv_DR2_TV_vjp_dev(size_t M, size_t N, size_t B, const double *unary, dou
     });
 }
 
+int proxtv_PD_TV_vjp_dev(int which, const double *y, const double *lambdas, const double *dims, const int *ns, int nds, int npen, int iters,
+                         const double *g, double *x, double *gy, double *glam, void *stream) {
+    return guarded("proxtv_PD_TV_vjp_dev", nullptr, 1, [&] {
+        if (which != 0 && which != 1) reject("which: 0 (PD2_TV) or 1 (PD_TV)");
+        if (iters < 1) reject("iters: the iteration count of the forward solve (info[0]), at least 1");
+        if (npen < 1) reject("at least one penalty term is required");
+        if (which == 0 && npen > 2) reject("PD2 works with 1 or 2 penalties");
+        check_dims(dims, npen, nds);
+        const size_t n = (size_t)total(ns, nds);
+        if (n == 0) return;
+        if (!y || !g || !gy) reject("y, g and gy are required");
+        // every array is read or written while others are: none may overlap another, except that gy may BE g (vjp.hip)
+        struct Span { const double *p; bool out; const char *name; };
+        const Span spans[] = {{y, false, "y"}, {g, false, "g"}, {x, true, "x"}, {gy, true, "gy"}};
+        for (const Span &o : spans) {
+            if (!o.out || !o.p) continue;
+            for (const Span &i : spans) {
+                if (&i == &o || !i.p || (&o == &spans[3] && &i == &spans[1] && gy == g)) continue;
+                if (i.out && &i > &o) continue;   // (a pair of outputs: once)
+                if (i.p < o.p + n && o.p < i.p + n) {
+                    set_error("%s overlaps %s (only gy may alias g, and then exactly)", o.name, i.name);
+                    throw HipFailure{hipErrorInvalidValue};
+                }
+            }
+        }
+        const size_t tape = pd_vjp_tape_bytes(which, ns, nds, npen, iters);
+        if (tape > pool_cap_bytes()) {
+            set_error("the tape of sweep outputs needs %zu bytes, the scratch pool is capped at %zu (PROXTV_POOL_CAP_MB)", tape, pool_cap_bytes());
+            throw HipFailure{hipErrorOutOfMemory};
+        }
+        hipStream_t st = pick(stream);
+        SolveScope scope(st);
+        pd_vjp(which, y, lambdas, dims, ns, nds, npen, iters, g, x, gy, glam, st);
+        scope.finish();
+    });
+}
+
 int proxtv_tvp_fibres_dev(const double *in, double *out, const int *ns, int nds, int dim, double lambda, double p,
                           void *stream) {
     return guarded("proxtv_tvp_fibres_dev", nullptr, 1, [&] {

@@ -31,6 +31,14 @@ size_t dr2_vjp_tape_bytes(size_t M, size_t N, size_t B, int maxit);
 void dr2_vjp(size_t M, size_t N, size_t B, const double *unary, double W1, double W2, const double *W1m, const double *W2m, const double *g,
              double *out, double *gU, double *gW1, double *gW2, double *glam, int maxit, hipStream_t s);
 
+// the derivative of pd2 (which == 0; npen <= 2) / pd (which == 1) with TV-L1 terms (vjp.hip): runs `iters` iterations of the
+// unfused recurrence -- no stopping test, nothing read back -- with every sweep output kept in pool scratch (pd_vjp_tape_bytes; the caller
+// checks it against pool_cap_bytes), then the reverse sweeps.  lambdas / dims: host, as pd2 / pd take them.  x / glam may be null; gy may be
+// g, no other overlap.  glam: HOST double[npen], the gradient in `lambdas` as passed.  Returns with the stream drained.
+size_t pd_vjp_tape_bytes(int which, const int *ns, int nds, int npen, int iters);
+void pd_vjp(int which, const double *y, const double *lambdas, const double *dims, const int *ns, int nds, int npen, int iters, const double *g,
+            double *x, double *gy, double *glam, hipStream_t s);
+
 // out = prox along `dim` with the TV-L1 (norm 1: the sweep kernels) or TV-L2 (norm 2: tv2.hip) penalty; in != out
 void prox_fibres(const double *in, double *out, const int *ns, int nds, int dim, double lam, double norm, hipStream_t s);
 

@@ -14,6 +14,9 @@
 // forward recurrence with its sweep outputs kept, then the same three phases once per sweep, last sweep first.  The pointwise work of
 // the reverse recurrence rides in phase C as epilogue variants of the two kernels (VJP_DR_ROW / VJP_DR_COL below), the way ops.hpp
 // folds the forward's into the sweeps: a reverse iteration is two fibre VJPs and no other pass over the arrays.
+//
+// The third part is the derivative of the two Dykstra loops behind tvgen (proxtv_PD_TV_vjp_dev), built the same way:
+// VJP_PD2 for the two-term loop, VJP_PD_SUMMARY / VJP_PD for the parallel one, whose cotangent is formed on load in phases A and C.
 #include "solvers.hpp"
 #include "vjpcore.hpp"
 
@@ -43,14 +46,32 @@ static_assert((kVjpL & (kVjpL - 1)) == 0, "the staging loops split an element in
 //                ... of the final sweep, g = the caller's cotangent:                          gU  = a ;  c = a       ;  gx = -a
 //   VJP_DR_COL   the column sweep behind it, g = c, gx = what the row sweep left:             gx += a
 // and gw = or += the per-edge gradient.  Every element is read and written by the one lane that owns it.
-enum { VJP_SUMMARY = 0, VJP_PLAIN = 1, VJP_DR_ROW = 2, VJP_DR_COL = 3 };
+// The Dykstra loops (pd_vjp below):
+//   VJP_PD2      a sweep of the two-term loop, g = the running difference D, in place:       gx = a - g   (and, with gU: gU += a)
+//                ... of the last iteration, where the state is still empty:                   gx = a (no gU) ;  gx = a - g, gU = a
+//   VJP_PD       term i of the parallel loop: the cotangent is pi = scale g - zeta, formed on load (g = chi, shared by the terms; phase
+//                A is VJP_PD_SUMMARY, the same load), gx = zeta_i in place:                   gx = zeta + a ;  gU += gx (final: gU = gx)
+//                (zeta == null: the last iteration's form, every zeta_i still 0)
+enum { VJP_SUMMARY = 0, VJP_PLAIN = 1, VJP_DR_ROW = 2, VJP_DR_COL = 3, VJP_PD2 = 4, VJP_PD_SUMMARY = 5, VJP_PD = 6 };
 struct VjpEpi {
-    double *gU = nullptr, *c = nullptr;   // VJP_DR_ROW
-    int final = 0;                        // VJP_DR_ROW: the final sweep's form
+    double *gU = nullptr, *c = nullptr;   // VJP_DR_ROW ; gU: VJP_PD2 (gy) and VJP_PD (the running sum of the zeta_i)
+    int final = 0;                        // VJP_DR_ROW: the final sweep's form ; VJP_PD2: the last iteration's ; VJP_PD: the iteration's first term
     int add_gw = 0;                       // gw accumulates
+    const double *zeta = nullptr;         // VJP_PD
+    double scale = 0.0;                   // VJP_PD: 1 / P
 };
 
-// g0: the cotangent the sample came in with (VJP_DR_ROW, not final; anything otherwise)
+constexpr bool vjp_writes(int mode) { return mode != VJP_SUMMARY && mode != VJP_PD_SUMMARY; }
+constexpr bool vjp_forms_cotangent(int mode) { return mode == VJP_PD_SUMMARY || mode == VJP_PD; }
+// modes whose write-out wants a second value per sample next to the mean: the cotangent as it came in, or (VJP_PD) zeta
+constexpr bool vjp_keeps(int mode) { return mode == VJP_DR_ROW || mode == VJP_PD2 || mode == VJP_PD; }
+
+// the cotangent of sample i the way phases A and C of VJP_PD both form it: one fused multiply-add, so both see the same bits
+__device__ __forceinline__ double vjp_pd_cotangent(const VjpEpi &e, const double *g, long i, double zeta) {
+    return __builtin_fma(g[i], e.scale, -zeta);
+}
+
+// g0: the cotangent the sample came in with (VJP_DR_ROW, not final; VJP_PD2), zeta (VJP_PD); anything otherwise
 template <int MODE>
 __device__ __forceinline__ void vjp_store(const VjpEpi &e, double *gx, long i, double a, double g0) {
     if constexpr (MODE == VJP_DR_ROW) {
@@ -65,6 +86,17 @@ __device__ __forceinline__ void vjp_store(const VjpEpi &e, double *gx, long i, d
         }
     } else if constexpr (MODE == VJP_DR_COL) {
         gx[i] += a;
+    } else if constexpr (MODE == VJP_PD2) {
+        if (e.gU) {
+            e.gU[i] = e.final ? a : e.gU[i] + a;
+            gx[i] = a - g0;
+        } else {
+            gx[i] = e.final ? a : a - g0;
+        }
+    } else if constexpr (MODE == VJP_PD) {
+        const double z = g0 + a;
+        gx[i] = z;
+        e.gU[i] = e.final ? z : e.gU[i] + z;
     } else {
         gx[i] = a;
     }
@@ -80,7 +112,7 @@ __device__ __forceinline__ void vjp_store_gw(const VjpEpi &e, double *gw, long i
 template <int MODE>
 __global__ __launch_bounds__(256) void vjp_strided_kernel(const double *y, const double *g, double *gx, double *gw, FibreGeom geo, int nch,
                                                           Summary *S, const Resolved *R, VjpEpi epi) {
-    constexpr bool WRITE = MODE != VJP_SUMMARY;
+    constexpr bool WRITE = vjp_writes(MODE), KEEP = vjp_keeps(MODE);
     const long unit = (long)blockIdx.x * 4 + (threadIdx.x >> 6), groups = (geo.count + 63) / 64;
     if (unit >= groups * nch) return;
     long grp, c;
@@ -93,9 +125,18 @@ __global__ __launch_bounds__(256) void vjp_strided_kernel(const double *y, const
     const bool has_next = k0 + clen < geo.len;
     const long base = blk * geo.inc * geo.len + off + (long)k0 * geo.inc, inc = geo.inc;
     Chunk<kVjpL> ch;
-    vjp::chunk_load(ch, clen, has_next, [&](int k) { return y[base + (long)k * inc]; }, [&](int k) { return g[base + (long)k * inc]; });
-    double g0[MODE == VJP_DR_ROW ? kVjpL : 1] = {};   // the cotangents as they came in: the row epilogue wants them next to the means
-    if constexpr (MODE == VJP_DR_ROW) {
+    double g0[KEEP ? kVjpL : 1] = {};   // the cotangents as they came in (VJP_PD: zeta): the epilogue wants them next to the means
+    if constexpr (vjp_forms_cotangent(MODE)) {
+        vjp::chunk_load(ch, clen, has_next, [&](int k) { return y[base + (long)k * inc]; }, [&](int k) {
+            const long i = base + (long)k * inc;
+            const double z = epi.zeta ? epi.zeta[i] : 0.0;
+            if constexpr (MODE == VJP_PD) g0[k] = z;
+            return vjp_pd_cotangent(epi, g, i, z);
+        });
+    } else {
+        vjp::chunk_load(ch, clen, has_next, [&](int k) { return y[base + (long)k * inc]; }, [&](int k) { return g[base + (long)k * inc]; });
+    }
+    if constexpr (MODE == VJP_DR_ROW || MODE == VJP_PD2) {
 #pragma unroll
         for (int k = 0; k < kVjpL; k++)
             if (k < clen) g0[k] = ch.g[k];
@@ -110,7 +151,7 @@ __global__ __launch_bounds__(256) void vjp_strided_kernel(const double *y, const
     vjp::chunk_means(ch, R[idx], gw != nullptr, [&](int k, double v) { vjp_store_gw<MODE>(epi, gw, wbase + (long)k * inc, v); });
 #pragma unroll
     for (int k = 0; k < kVjpL; k++)
-        if (k < clen) vjp_store<MODE>(epi, gx, base + (long)k * inc, ch.g[k], g0[MODE == VJP_DR_ROW ? k : 0]);
+        if (k < clen) vjp_store<MODE>(epi, gx, base + (long)k * inc, ch.g[k], g0[KEEP ? k : 0]);
 }
 
 // one lane per fibre, over its chunks in order
@@ -126,7 +167,7 @@ __global__ __launch_bounds__(64) void vjp_resolve_strided_kernel(const Summary *
 template <int MODE>
 __global__ __launch_bounds__(64) void vjp_contig_kernel(const double *y, const double *g, double *gx, double *gw, int len, long count, int nch,
                                                         Summary *S, const Resolved *R, VjpEpi epi) {
-    constexpr bool WRITE = MODE != VJP_SUMMARY;
+    constexpr bool WRITE = vjp_writes(MODE);
     __shared__ double ty[64 * kVjpRow], tg[64 * kVjpRow];
     const int lane = threadIdx.x;
     const long unit = (long)blockIdx.x * 64 + lane;
@@ -143,7 +184,8 @@ __global__ __launch_bounds__(64) void vjp_contig_kernel(const double *y, const d
         const long b = __shfl(base, src);
         if (k < __shfl(clen, src)) {
             ty[src * kVjpRow + k] = y[b + k];
-            tg[src * kVjpRow + k] = g[b + k];
+            if constexpr (vjp_forms_cotangent(MODE)) tg[src * kVjpRow + k] = vjp_pd_cotangent(epi, g, b + k, epi.zeta ? epi.zeta[b + k] : 0.0);
+            else tg[src * kVjpRow + k] = g[b + k];
         }
     }
     if (has_next) ty[lane * kVjpRow + clen] = y[base + clen];
@@ -181,6 +223,10 @@ __global__ __launch_bounds__(64) void vjp_contig_kernel(const double *y, const d
             double g0 = 0.0;
             if constexpr (MODE == VJP_DR_ROW)
                 if (!epi.final) g0 = g[b + k];
+            if constexpr (MODE == VJP_PD2)
+                if (epi.gU || !epi.final) g0 = g[b + k];
+            if constexpr (MODE == VJP_PD)
+                if (epi.zeta) g0 = epi.zeta[b + k];
             vjp_store<MODE>(epi, gx, b + k, tg[src * kVjpRow + k], g0);
         }
         if (want_gw && k < nw) vjp_store_gw<MODE>(epi, gw, wb + k, ty[src * kVjpRow + k]);
@@ -240,17 +286,19 @@ namespace {
 template <int MODE>
 void vjp_launch(const double *y, const double *g, double *gx, double *gw, int *nseg, const FibreGeom &geo, Summary *S, Resolved *R,
                 const VjpEpi &epi, hipStream_t s) {
+    constexpr int A = MODE == VJP_PD ? VJP_PD_SUMMARY : VJP_SUMMARY;   // (phase A forms the cotangent the way phase C will)
+    const VjpEpi epa = MODE == VJP_PD ? epi : VjpEpi{};
     const int nch = (geo.len + kVjpL - 1) / kVjpL;
     const long units = geo.count * nch;
     if (geo.inc == 1) {
         const unsigned blocks = (unsigned)((units + 63) / 64), fibres4 = (unsigned)((geo.count + 3) / 4);
-        hipLaunchKernelGGL(vjp_contig_kernel<VJP_SUMMARY>, dim3(blocks), dim3(64), 0, s, y, g, gx, gw, geo.len, geo.count, nch, S, R, VjpEpi{});
+        hipLaunchKernelGGL(vjp_contig_kernel<A>, dim3(blocks), dim3(64), 0, s, y, g, gx, gw, geo.len, geo.count, nch, S, R, epa);
         hipLaunchKernelGGL(vjp_resolve_contig_kernel, dim3(fibres4), dim3(256), 0, s, S, R, nch, geo.count, nseg);
         if (gx) hipLaunchKernelGGL(vjp_contig_kernel<MODE>, dim3(blocks), dim3(64), 0, s, y, g, gx, gw, geo.len, geo.count, nch, S, R, epi);
     } else {
         const long waves = ((geo.count + 63) / 64) * nch;
         const unsigned blocks = (unsigned)((waves + 3) / 4), fibres64 = (unsigned)((geo.count + 63) / 64);
-        hipLaunchKernelGGL(vjp_strided_kernel<VJP_SUMMARY>, dim3(blocks), dim3(256), 0, s, y, g, gx, gw, geo, nch, S, R, VjpEpi{});
+        hipLaunchKernelGGL(vjp_strided_kernel<A>, dim3(blocks), dim3(256), 0, s, y, g, gx, gw, geo, nch, S, R, epa);
         hipLaunchKernelGGL(vjp_resolve_strided_kernel, dim3(fibres64), dim3(64), 0, s, S, R, nch, geo.count, nseg);
         if (gx) hipLaunchKernelGGL(vjp_strided_kernel<MODE>, dim3(blocks), dim3(256), 0, s, y, g, gx, gw, geo, nch, S, R, epi);
     }
@@ -366,6 +414,190 @@ void dr2_vjp(size_t M, size_t N, size_t B, const double *unary, double W1, doubl
         }
     }
     PTV_HIP(hipStreamSynchronize(s));   // (the scratch goes back to the pool behind this)
+}
+
+// ---- the derivative of the Dykstra loops behind tvgen ------------------------------------------------------------------------------
+namespace {
+
+long total(const int *ns, int nds) {
+    long n = 1;
+    for (int i = 0; i < nds; i++) n *= ns[i];
+    return n;
+}
+
+}  // namespace
+
+size_t pd_vjp_tape_bytes(int which, const int *ns, int nds, int npen, int iters) {
+    const size_t sweeps = which == 0 ? (npen == 1 ? 1 : 2 * (size_t)iters) : (size_t)npen * (size_t)iters;
+    return sweeps * sizeof(double) * (size_t)total(ns, nds);
+}
+
+namespace {
+
+// the edges along a term's dimension, and what gw of a sweep along it is handed (null: nobody asks, or there are none)
+struct TermGw {
+    long edges = 0;
+    std::unique_ptr<Scratch> buf;
+    double *d() const { return buf ? buf->d() : nullptr; }
+};
+void term_gw(TermGw &t, const FibreGeom &geo, bool wanted) {
+    t.edges = geo.count * (long)(geo.len - 1);
+    if (wanted && t.edges > 0) t.buf.reset(new Scratch(sizeof(double) * (size_t)t.edges));
+}
+// glam[i] = the sum of term i's per-edge gradients, in sum_to's fixed layout (0 where there are no edges)
+void sum_terms(const std::vector<TermGw> &gw, double *glam, hipStream_t s) {
+    const size_t P = gw.size();
+    Scratch partials(sizeof(double) * kReduceBlocks), sums(sizeof(double) * P);
+    std::vector<double> h(P, 0.0);
+    for (size_t i = 0; i < P; i++) {
+        if (!gw[i].d()) continue;
+        sum_to(gw[i].d(), gw[i].edges, 1, partials.d(), sums.d() + i, s);
+        PTV_HIP(hipMemcpyAsync(&h[i], sums.d() + i, sizeof(double), hipMemcpyDeviceToHost, s));
+    }
+    PTV_HIP(hipStreamSynchronize(s));
+    for (size_t i = 0; i < P; i++) glam[i] = h[i];
+}
+
+// Two-term proximal Dykstra (pd2 of solvers.hip, TV-L1 terms), K iterations with the sweep outputs z_k, x'_k kept:
+//   x = y, p = q = 0 ; repeat: z = prox_0(x + p), p += x - z ; x' = prox_1(z + q), q += z - x' ; x = x'
+// Reverse.  With X, Pb, Qb the cotangents of x, p, q (X = g, Pb = Qb = 0 behind the last iteration), an iteration is
+//   a = P_1 (X - Qb) ; Zc = a + Qb - Pb ; Qb += a ; b = P_0 Zc ; X = Pb = Pb + b
+// X and Pb are one array from the first reverse iteration on, so the state is X and the difference D = X - Qb, and in those
+//   a = P_1 D ; Zc = a - D  (last iteration: Zc = a) ; b = P_0 Zc ; X += b  (last: X = b) ; D = b - Zc
+// two launches of three phases, D rewritten in place by both, X = gy touched by the second alone.  One term: a single sweep.
+void pd2_vjp(const double *y, const double *lambdas, const double *dims, const int *ns, int nds, int npen, int K, const double *g, double *x,
+             double *gy, double *glam, hipStream_t s) {
+    const long n = total(ns, nds);
+    const size_t bytes = sizeof(double) * (size_t)n;
+    const int d0 = (int)(dims[0] - 1), d1 = npen >= 2 ? (int)(dims[1] - 1) : d0;
+    const FibreGeom g0 = fibres_along(ns, nds, d0), g1 = fibres_along(ns, nds, d1);
+    Scratch tape(pd_vjp_tape_bytes(0, ns, nds, npen, K));
+    std::vector<TermGw> gw((size_t)npen);
+    term_gw(gw[0], g0, glam != nullptr);
+    if (npen >= 2) term_gw(gw[1], g1, glam != nullptr);
+    const long units = std::max(vjp_units(g0), vjp_units(g1));
+    Scratch S(sizeof(Summary) * (size_t)units), R(sizeof(Resolved) * (size_t)units);
+    if (npen == 1) {   // (x + p stays y: every iteration repeats the first)
+        tv1_fibres(y, tape.d(), ns, nds, d0, lambdas[0], nullptr, s);
+        if (x) PTV_HIP(hipMemcpyAsync(x, tape.d(), bytes, hipMemcpyDeviceToDevice, s));
+        vjp_launch<VJP_PLAIN>(tape.d(), g, gy, gw[0].d(), nullptr, g0, S.as<Summary>(), R.as<Resolved>(), VjpEpi{}, s);
+    } else {
+        Scratch t(bytes), p(bytes), q(bytes);
+        auto zk = [&](int k) { return tape.d() + (size_t)(2 * k) * (size_t)n; };
+        auto xk = [&](int k) { return tape.d() + (size_t)(2 * k + 1) * (size_t)n; };
+        const double *xc = y;
+        for (int k = 0; k < K; k++) {
+            if (k == 0) {   // p = q = 0
+                tv1_fibres(y, zk(0), ns, nds, d0, lambdas[0], nullptr, s);
+                lincomb(p.d(), y, 1.0, zk(0), -1.0, nullptr, 0, nullptr, 0, n, s);
+                tv1_fibres(zk(0), xk(0), ns, nds, d1, lambdas[1], nullptr, s);
+                lincomb(q.d(), zk(0), 1.0, xk(0), -1.0, nullptr, 0, nullptr, 0, n, s);
+            } else {
+                lincomb(t.d(), xc, 1.0, p.d(), 1.0, nullptr, 0, nullptr, 0, n, s);
+                tv1_fibres(t.d(), zk(k), ns, nds, d0, lambdas[0], nullptr, s);
+                lincomb(p.d(), p.d(), 1.0, xc, 1.0, zk(k), -1.0, nullptr, 0, n, s);
+                lincomb(t.d(), zk(k), 1.0, q.d(), 1.0, nullptr, 0, nullptr, 0, n, s);
+                tv1_fibres(t.d(), xk(k), ns, nds, d1, lambdas[1], nullptr, s);
+                lincomb(q.d(), q.d(), 1.0, zk(k), 1.0, xk(k), -1.0, nullptr, 0, n, s);
+            }
+            xc = xk(k);
+        }
+        if (x) PTV_HIP(hipMemcpyAsync(x, xc, bytes, hipMemcpyDeviceToDevice, s));
+        double *D = t.d();   // t is free again
+        for (int k = K - 1; k >= 0; k--) {
+            VjpEpi second, first;
+            second.final = first.final = k == K - 1;
+            second.add_gw = first.add_gw = k != K - 1;
+            first.gU = gy;
+            vjp_launch<VJP_PD2>(xk(k), second.final ? g : D, D, gw[1].d(), nullptr, g1, S.as<Summary>(), R.as<Resolved>(), second, s);
+            vjp_launch<VJP_PD2>(zk(k), D, D, gw[0].d(), nullptr, g0, S.as<Summary>(), R.as<Resolved>(), first, s);
+        }
+    }
+    if (glam) sum_terms(gw, glam, s);
+    PTV_HIP(hipStreamSynchronize(s));   // (the scratch goes back to the pool behind this)
+}
+
+// Parallel proximal Dykstra (pd_like(false, ...) of solvers.hip, TV-L1 terms), K iterations with the P sweep outputs p_i^k kept:
+//   z_i = y ; repeat: p_i = prox_i(z_i) ; x = sum_i p_i / P ; z_i += x - p_i          (the combine is the fused loop's own kernel)
+// Reverse, zeta_i the cotangent of z_i (0 behind the last iteration) and chi = [g, the last iteration] + sum_i zeta_i:
+//   for every i:  pi = chi / P - zeta_i ; a = P_i pi ; zeta_i += a ; chi' (+)= zeta_i             end: gy = chi'
+// one launch of three phases per term: pi is formed on load in phases A and C (chi is read by every term, so the sum for the next
+// iteration grows in a second array; the two change places), zeta_i is rewritten in place in the arrays the forward kept z_i in.
+void pdp_vjp(const double *y, const double *lambdas, const double *dims, const int *ns, int nds, int P, int K, const double *g, double *x,
+             double *gy, double *glam, hipStream_t s) {
+    const long n = total(ns, nds);
+    const size_t bytes = sizeof(double) * (size_t)n;
+    Scratch tape(pd_vjp_tape_bytes(1, ns, nds, P, K));
+    auto pk = [&](int k, int i) { return tape.d() + ((size_t)k * (size_t)P + (size_t)i) * (size_t)n; };
+    std::vector<std::unique_ptr<Scratch>> z;
+    std::vector<FibreGeom> geo;
+    std::vector<TermGw> gw((size_t)P);
+    long units = 0;
+    for (int i = 0; i < P; i++) {
+        z.emplace_back(new Scratch(bytes));
+        geo.push_back(fibres_along(ns, nds, (int)(dims[i] - 1)));
+        term_gw(gw[(size_t)i], geo.back(), glam != nullptr);
+        units = std::max(units, vjp_units(geo.back()));
+        PTV_HIP(hipMemcpyAsync(z.back()->d(), y, bytes, hipMemcpyDeviceToDevice, s));
+    }
+    Scratch xa(bytes), xb(bytes), partials(sizeof(double) * kReduceBlocks), acc(sizeof(double));
+    // more terms than a kernel-argument pack holds: the combine reads its addresses from a table in HBM, [P] p_i^k then [P] z_i per iteration
+    std::unique_ptr<Scratch> table;
+    if (P > kMaxTerms) {
+        std::vector<double *> host;
+        for (int k = 0; k < K; k++) {
+            for (int i = 0; i < P; i++) host.push_back(pk(k, i));
+            for (int i = 0; i < P; i++) host.push_back(z[(size_t)i]->d());
+        }
+        table.reset(new Scratch(sizeof(double *) * host.size()));
+        PTV_HIP(hipMemcpyAsync(table->as<double *>(), host.data(), sizeof(double *) * host.size(), hipMemcpyHostToDevice, s));
+        PTV_HIP(hipStreamSynchronize(s));   // (`host` lives on this frame)
+    }
+    PTV_HIP(hipMemsetAsync(xa.d(), 0, bytes, s));
+    for (int k = 0; k < K; k++) {
+        PtrPack pp{}, zp{};
+        for (int i = 0; i < P; i++) {
+            tv1_fibres(z[(size_t)i]->d(), pk(k, i), ns, nds, (int)(dims[i] - 1), lambdas[i], nullptr, s);
+            if (i < kMaxTerms) {
+                pp.v[i] = pk(k, i);
+                zp.v[i] = z[(size_t)i]->d();
+            }
+        }
+        if (table) pd_combine_many(table->as<double *>() + (size_t)k * 2 * (size_t)P, xa.d(), xa.d(), P, n, partials.d(), acc.d(), false, s);
+        else       pd_combine(pp, zp, xa.d(), xa.d(), P, n, partials.d(), acc.d(), s);
+    }
+    if (x) PTV_HIP(hipMemcpyAsync(x, xa.d(), bytes, hipMemcpyDeviceToDevice, s));
+
+    Scratch S(sizeof(Summary) * (size_t)units), R(sizeof(Resolved) * (size_t)units);
+    const double *chi = g;
+    double *next = nullptr;
+    for (int k = K - 1; k >= 0; k--) {
+        // the last sum is gy itself, unless gy is the g that a single iteration is still reading
+        if (k == 0) next = (gy == g && K == 1) ? xa.d() : gy;
+        else        next = chi == xa.d() ? xb.d() : xa.d();
+        for (int i = 0; i < P; i++) {
+            VjpEpi e;
+            e.zeta = k == K - 1 ? nullptr : z[(size_t)i]->d();
+            e.scale = 1.0 / P;
+            e.gU = next;
+            e.final = i == 0;
+            e.add_gw = k != K - 1;
+            vjp_launch<VJP_PD>(pk(k, i), chi, z[(size_t)i]->d(), gw[(size_t)i].d(), nullptr, geo[(size_t)i], S.as<Summary>(), R.as<Resolved>(), e, s);
+        }
+        chi = next;
+    }
+    if (next != gy) PTV_HIP(hipMemcpyAsync(gy, next, bytes, hipMemcpyDeviceToDevice, s));
+    if (glam) sum_terms(gw, glam, s);
+    PTV_HIP(hipStreamSynchronize(s));   // (the scratch goes back to the pool behind this)
+}
+
+}  // namespace
+
+void pd_vjp(int which, const double *y, const double *lambdas, const double *dims, const int *ns, int nds, int npen, int iters, const double *g,
+            double *x, double *gy, double *glam, hipStream_t s) {
+    if (total(ns, nds) == 0) return;
+    if (which == 0) pd2_vjp(y, lambdas, dims, ns, nds, npen, iters, g, x, gy, glam, s);
+    else            pdp_vjp(y, lambdas, dims, ns, nds, npen, iters, g, x, gy, glam, s);
 }
 
 }  // namespace ptv

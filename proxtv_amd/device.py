@@ -309,6 +309,51 @@ def dr2_vjp(x, g, w_col, w_row=None, max_iters=0, weights_col=None, weights_row=
     return gx, gw_col, gw_row, glam, y
 
 
+def tvgen_vjp(x, g, ws, ds, iters, method=None, need_glam=False, need_y=False):
+    """The derivative of ``tvgen(x, ws, ds, method=method)`` applied to the cotangent `g` of its result: returns (gx, glam, y).
+
+    `iters` is the iteration count the forward solve reported (``info[0]``): the call runs exactly that many iterations of its own,
+    unfused recurrence and differentiates those -- the dependence of the count on the data through the stopping rule is not differentiated.
+    method follows tvgen's dispatch (None: 'pd2' for two terms, otherwise 'pd'); 'pdr' and 'yang' have no derivative.  gx is the gradient
+    in x.  glam (`need_glam`) is a numpy array with the gradient in every entry of `ws` as the user passes them (for 'pd' the library
+    works with ws * len(ws); the chain rule through that scaling is applied here).  y (`need_y`) is the forward result of the call's own
+    recurrence: tvgen's up to rounding.  One call: proxtv_PD_TV_vjp_dev (include/proxtv_amd.h), which keeps len(ws) * iters ('pd') or
+    2 * iters ('pd2') arrays of x's size in pool scratch while it runs.  A `g` in another layout is copied."""
+    _check(x, "x")
+    if not (isinstance(g, torch.Tensor) and g.is_cuda and g.dtype == torch.float64):
+        raise ValueError("g: expected a float64 CUDA tensor")
+    if g.device != x.device:
+        raise ValueError(f"g: lives on {g.device}, the input on {x.device}")
+    if tuple(g.shape) != tuple(x.shape):
+        raise ValueError(f"g: shape {tuple(g.shape)}, expected {tuple(x.shape)}")
+    if not _is_colmajor(g):
+        g = to_colmajor(g)
+    lam = np.array(ws, dtype=np.float64).reshape(-1)
+    dims = np.array(ds, dtype=np.float64).reshape(-1)
+    npen = lam.size
+    if dims.size != npen:
+        raise ValueError(f"ds: {dims.size} dimensions for {npen} penalties")
+    if method is None:
+        method = "pd2" if npen == 2 else "pd"
+    if method not in ("pd2", "pd"):
+        raise NotImplementedError(f"method {method!r} has no derivative (tvgen_vjp covers 'pd2' and 'pd')")
+    scale = float(npen) if method == "pd" else 1.0     # (device.tvgen hands PD_TV the npen-scaled penalties)
+    scaled = lam * scale
+    ns = np.array(x.shape, dtype=np.int32)
+    gx = colmajor_empty(x.shape, device=x.device)
+    y = colmajor_empty(x.shape, device=x.device) if need_y else None
+    glam = np.zeros(npen) if need_glam else None
+    ptr = lambda t: t.data_ptr() if t is not None and t.numel() else 0   # noqa: E731
+    with torch.cuda.device(x.device):
+        lib = _lib.require_device()
+        lib.proxtv_PD_TV_vjp_dev(0 if method == "pd2" else 1, ptr(x), scaled.ctypes.data, dims.ctypes.data, ns.ctypes.data, x.dim(), npen,
+                                 int(iters), ptr(g), ptr(y), ptr(gx), glam.ctypes.data if need_glam else 0, _stream(x.device))
+    _lib.check("device.tvgen_vjp")
+    if glam is not None:
+        glam *= scale
+    return gx, glam, y
+
+
 def tv1_fibres_dof(y, dim):
     """Segments of every fibre of ``y = tv1_fibres(x, w, dim)`` along `dim` (int32, the shape of `y` without `dim`): the trace of the
     prox's Jacobian, i.e. the degrees of freedom SURE needs.  One pass over `y`; nothing else is computed."""
