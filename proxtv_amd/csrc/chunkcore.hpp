@@ -531,17 +531,41 @@ __device__ __forceinline__ void settle_short_runs(const EdgeMasks &m, unsigned &
     BT = m.P & BE;
     WS = K & ~Kp & ~(K >> 2);
 }
+// The fibre's free end in a lane's masks (the segment that holds the fibre's last sample): the mirror image of the free start.  The
+// string's height behind sample len - 1 is 0 and nothing lies beyond it, so the edge behind the last sample -- bit f = len - cs +
+// kEdgeBias of the lane with chunk start cs: its own, one of its neighbours', or none of its 32 -- delimits the last run as a bend known
+// a priori would, and no bit past it stands for anything (the window's rows there are copies of the last sample).
+// f < 0: the lane's whole mask lies past the fibre; f > 31: the end is out of its sight and nothing changes.
+__device__ __forceinline__ void free_end_edges(EdgeMasks &m, int f) {
+    if (f > 31) return;
+    const unsigned at = f < 0 ? 0u : (1u << f), below = at ? at - 1u : 0u;
+    m.K = (m.K & below) | at;
+    m.P &= below; m.N &= below; m.B &= below;
+}
+// ... and in what settle_short_runs makes of them: no rule of thumb across the free end -- the inner edge of a last run of two samples
+// (bit f - 1) is a bend only if it is one a priori -- a last run of two samples and more is walked, however short (its first edge, bit
+// f - 2, joins WS), and no run starts at the free end or behind it.
+__device__ __forceinline__ void free_end_settle(const EdgeMasks &m, int f, unsigned &BE, unsigned &BT, unsigned &WS) {
+    if (f > 31) return;
+    if (f < 1) { WS = 0u; return; }   // (BE holds the end's own bit at most, BT nothing)
+    const unsigned in = 1u << (f - 1), two = in >> 1;
+    BE = (BE & ~in) | (m.K & in);
+    BT = (BT & ~in) | (m.P & m.K & in);
+    WS = (WS & (in - 1u)) | (m.K & ~(m.K >> 1) & two);
+}
 // a run to walk, as the lane that owns its first sample describes it to the lane that will walk it
 struct RunEntry {
     unsigned word;
-    __device__ __forceinline__ static RunEntry make(int lane, int b, int e, int type, bool free_start) {
-        return RunEntry{(unsigned)lane | ((unsigned)b << 6) | ((unsigned)e << 11) | ((unsigned)type << 16) | ((unsigned)free_start << 17)};
+    __device__ __forceinline__ static RunEntry make(int lane, int b, int e, int type, bool free_start, bool free_end = false) {
+        return RunEntry{(unsigned)lane | ((unsigned)b << 6) | ((unsigned)e << 11) | ((unsigned)type << 16) | ((unsigned)free_start << 17) |
+                        ((unsigned)free_end << 18)};
     }
     __device__ __forceinline__ int lane() const { return (int)(word & 63u); }
     __device__ __forceinline__ int b() const { return (int)((word >> 6) & 31u); }     // bit of the run's first edge in its owner's mask
     __device__ __forceinline__ int e() const { return (int)((word >> 11) & 31u); }    // ... of the bend that closes it
     __device__ __forceinline__ int type() const { return (int)((word >> 16) & 1u); }
     __device__ __forceinline__ bool free_start() const { return (word >> 17) & 1u; }
+    __device__ __forceinline__ bool free_end() const { return (word >> 18) & 1u; }    // closed by the fibre's end, not by a bend
 };
 // the end of the run that starts at edge b: the next bend known a priori (-1: none inside the mask, or further than a lane takes)
 __device__ __forceinline__ int run_end(unsigned K, int b) {

@@ -225,7 +225,8 @@ __global__ __launch_bounds__(64 * kAlongWaves) void sweep_along_kernel(SweepArgs
     ChunkRec rec;
     bool certain = false;
     // ---- RUNS: the segment cut at the bends known a priori, run by run (chunkcore.hpp "known runs") ------------------------------------
-    // Interior segments only (every row of the window exists; the fibre's last sample, with its own tests, is another segment's).  Four
+    // Interior segments (every row of the window exists) and the end segment, whose free end delimits its last run the way the fibre's
+    // start delimits the first (the one segment in between, whose look-ahead rows do not all exist, stays speculative).  Four
     // phases, all inside the wave: (1) every lane looks at the edges of its chunk -- bends known a priori, and what decides a run of two
     // samples -- and borrows its neighbours' for the runs that cross into and out of its chunk; (2) runs of three and more samples are
     // listed; (3) lane i walks run i from its first bend to the closing one; what it finds goes to the chunks it belongs to; (4) every
@@ -235,11 +236,14 @@ __global__ __launch_bounds__(64 * kAlongWaves) void sweep_along_kernel(SweepArgs
     // speculative walk below as if nothing had happened.
     bool solved = false;
     if constexpr (RUNS) {
-        if (interior && p.lam > 0.0 && !(plan.ablate & 1)) {
+        if ((interior || endseg) && p.lam > 0.0 && !(plan.ablate & 1)) {
             typedef __attribute__((address_space(3))) unsigned lds_uint;   // (LDS instructions, not flat ones: the atomics below are ds_or / ds_max)
             lds_uint *rl = (lds_uint *)(reinterpret_cast<unsigned *>(rtab + TS) + wave * kRunsWords);   // [0, 64) runs ; [64, 128) ends ; [128, 192) types ; [192] the bend before the segment
             constexpr unsigned CM = (1u << C) - 1u;
             const bool free0 = sg == 0 && lane == 0;   // the fibre starts here: no bend, height 0
+            // `endseg`: the fibre ends in this segment, a free end like its start -- the edge behind sample len - 1 is bit fend of this lane's
+            // masks (chunkcore.hpp free_end_edges: its own, a neighbour's, or out of sight), the lanes past the last chunk own nothing
+            const int fend = len - cs + kEdgeBias, uend = len - 1 - cs;
             // (1) edges
             const EdgeMasks own = own_edges<C>(win, cs, p.lam);
             EdgeMasks pv, nx;
@@ -249,7 +253,7 @@ __global__ __launch_bounds__(64 * kAlongWaves) void sweep_along_kernel(SweepArgs
             nx.N = (unsigned)__shfl_down((int)own.N, 1); nx.B = (unsigned)__shfl_down((int)own.B, 1);
             {   // the edges no chunk of the segment owns: the T = 8 behind it (lanes 0 .. 7), the two before it (lanes 8, 9)
                 unsigned k = 0, pp = 0, nn = 0, bb = 0;
-                if (lane < 8) one_edge(win.y(seg_e - 1 + lane), win.y(seg_e + lane), p.lam, k, pp, nn, bb);
+                if (lane < 8) { if (interior) one_edge(win.y(seg_e - 1 + lane), win.y(seg_e + lane), p.lam, k, pp, nn, bb); }   // (endseg: they do not exist)
                 else if (lane < 10 && sg > 0) one_edge(win.y(seg_s - 11 + lane), win.y(seg_s - 10 + lane), p.lam, k, pp, nn, bb);
                 const unsigned xk = (unsigned)__ballot(k != 0u), xp = (unsigned)__ballot(pp != 0u), xn = (unsigned)__ballot(nn != 0u),
                                xb = (unsigned)__ballot(bb != 0u);
@@ -260,6 +264,7 @@ __global__ __launch_bounds__(64 * kAlongWaves) void sweep_along_kernel(SweepArgs
             m.K = edge_ext<C>(own.K, pv.K, nx.K); m.P = edge_ext<C>(own.P, pv.P, nx.P);
             m.N = edge_ext<C>(own.N, pv.N, nx.N); m.B = edge_ext<C>(own.B, pv.B, nx.B);
             if (free0) m.K = (m.K & ~7u) | 4u;   // (the fibre start delimits the first run like a bend; nothing lies before it)
+            if (endseg) free_end_edges(m, fend);  // (... and so does its end; nothing lies behind it: the rows there are copies of the last sample)
             unsigned BE, BT, WS;
             settle_short_runs(m, BE, BT, WS);
             if (free0) {   // no rule of thumb across the free end: the first run is walked unless it is one sample long
@@ -267,6 +272,7 @@ __global__ __launch_bounds__(64 * kAlongWaves) void sweep_along_kernel(SweepArgs
                 BT = (BT & ~8u) | (m.P & m.K & 8u);
                 WS = (WS & ~7u) | ((m.K & 8u) ? 0u : 4u);
             }
+            if (endseg) free_end_settle(m, fend, BE, BT, WS);   // (nor across this one: the last run is walked unless it is one sample long)
             // (2) this lane's runs: those whose first sample is its own; lane 0 also the one that comes in from before the segment
             unsigned dom = WS & ((1u << (C + kEdgeBias)) - 1u);
             if (lane > 0) dom &= ~3u;
@@ -287,7 +293,7 @@ __global__ __launch_bounds__(64 * kAlongWaves) void sweep_along_kernel(SweepArgs
                 dom &= dom - 1u;
                 const int e = run_end(m.K, b);
                 if (e < 0) fail = true;
-                else if (pos < 64) rl[pos] = RunEntry::make(lane, b, e, (int)((m.P >> b) & 1u), free0 && b == kEdgeBias).word;
+                else if (pos < 64) rl[pos] = RunEntry::make(lane, b, e, (int)((m.P >> b) & 1u), free0 && b == kEdgeBias, endseg && e == fend).word;
                 pos++;
             }
             bool go = __ballot(fail) == 0ull && total <= 64;
@@ -333,9 +339,13 @@ __global__ __launch_bounds__(64 * kAlongWaves) void sweep_along_kernel(SweepArgs
             if (go) {
                 const unsigned e_own = rl[64 + lane], t_own = rl[128 + lane];
                 const unsigned e_prev = lane ? rl[64 + lane - 1] : 0u, t_prev = lane ? rl[128 + lane - 1] : 0u;
-                const unsigned ends = ((BE >> (kEdgeBias + 1)) | e_own | (e_prev >> C)) & CM;
-                const unsigned types = ((BT >> (kEdgeBias + 1)) | t_own | (t_prev >> C)) & CM & ends;
-                const int lastb = ends ? 31 - __clz((int)ends) : -1;
+                // (endseg: rows past the fibre's last sample end no piece -- the partial last chunk, the lanes that own no chunk -- and the piece end
+                //  at sample len - 1 is no bend: the codes are those of the bends before it, as the walk leaves them)
+                const unsigned own_rows = !endseg ? CM : (!has_chunk ? 0u : (uend >= C - 1 ? CM : (2u << uend) - 1u));
+                const unsigned ends = ((BE >> (kEdgeBias + 1)) | e_own | (e_prev >> C)) & own_rows;
+                const unsigned types = ((BT >> (kEdgeBias + 1)) | t_own | (t_prev >> C)) & own_rows & ends;
+                const unsigned bends = (endseg && uend >= 0 && uend < C) ? (ends & ~(1u << uend)) : ends;
+                const int lastb = bends ? 31 - __clz((int)bends) : -1;
                 const link_t lcode = lastb >= 0 ? ((((link_t)(cs + lastb + 1)) << 1) | ((types >> lastb) & 1u)) : 0u;
                 // the bend the segment hangs on (lane 0 knows): the last one among the edges before its first sample -- known a priori,
                 // settled by rule, or found by the walk that came in from before the segment
@@ -356,9 +366,9 @@ __global__ __launch_bounds__(64 * kAlongWaves) void sweep_along_kernel(SweepArgs
                 const int src = lower ? 63 - __clzll((long long)lower) : 0;
                 const link_t from_lower = (link_t)__shfl((int)lcode, src);
                 const link_t mine = lower ? from_lower : hang;
-                bool bad_rec = mine == 0u && !(sg == 0 && lane == 0);   // (a first piece longer than a chunk at the fibre start: the walk's)
+                bool bad_rec = has_chunk && mine == 0u && !(sg == 0 && lane == 0);   // (a first piece longer than a chunk at the fibre start: the walk's)
                 link_t tail = 0u;
-                if (lane == 63 && !((ends >> (C - 1)) & 1u)) {
+                if (interior && lane == 63 && !((ends >> (C - 1)) & 1u)) {
                     // the piece that covers the segment's last sample ends behind it: at the first bend among the T edges there
                     const unsigned beyond = (BE >> (kEdgeBias + 1 + C)) | (e_own >> C), tbeyond = (BT >> (kEdgeBias + 1 + C)) | (t_own >> C);
                     if (beyond) {
@@ -369,12 +379,14 @@ __global__ __launch_bounds__(64 * kAlongWaves) void sweep_along_kernel(SweepArgs
                     }
                 }
                 if (__ballot(bad_rec) == 0ull) {
-                    rec.ends = ends;
-                    rec.types = types;
-                    rec.mine = mine;
-                    rec.next = lastb >= 0 ? lcode : mine;
-                    rec.last = lane == 63 && tail ? tail : rec.next;
-                    rec.done = true;
+                    if (has_chunk) {   // (the lanes past the fibre's last chunk keep their empty records)
+                        rec.ends = ends;
+                        rec.types = types;
+                        rec.mine = mine;
+                        rec.next = lastb >= 0 ? lcode : mine;
+                        rec.last = lane == 63 && tail ? tail : rec.next;
+                        rec.done = true;
+                    }
                     certain = true;
                     solved = true;
                     if (lane == 0) plan.dirty.note(5);   // (option "why": waves solved run by run)
@@ -515,13 +527,19 @@ __global__ __launch_bounds__(64 * kAlongWaves) void sweep_along_kernel(SweepArgs
         }
     } else
     if (endseg && !(plan.ablate & 2)) {   // (the same for the whole groups of 64 rows -- a scalar count -- and one tested group for the rest)
+        // The window's rows are read whether or not they leave (every row of the segment is staged, past the fibre's end as copies of the
+        // last sample), a batch of them in flight at once as in the interior form; only the global accesses are tested.  (With the LDS read
+        // under each group's test the compiler kept it there: seventeen times branch, read, wait for the LDS, store -- the end wave's stream-out
+        // took 1.04 us where the interior waves' takes 0.38, profiles/along_tail_wave_life.txt.)
         const long out0 = fbase + seg_s;
         const int nfull = (seg_e - seg_s) / G;
         const bool rest = gl < (seg_e - seg_s) - nfull * G;
 #pragma unroll
         for (int t0 = 0; t0 < C; t0 += UL) {
-            if (t0 > nfull) break;
             Ext ex[UL];
+            double v[UL];
+#pragma unroll
+            for (int u = 0; u < UL; u++) v[u] = t0 + u < C ? Yp[HZ + G * (t0 + u) + ul] : 0.0;
 #pragma unroll
             for (int u = 0; u < UL; u++) {
                 ex[u] = Ext{0, 0};
@@ -535,9 +553,8 @@ __global__ __launch_bounds__(64 * kAlongWaves) void sweep_along_kernel(SweepArgs
                 if (t0 + u >= C) continue;
                 const long idx = (out0 + G * (t0 + u)) + (long)ul;
                 if (t0 + u < nfull || (t0 + u == nfull && rest)) {
-                    const double v = Yp[HZ + G * (t0 + u) + ul];
-                    if (Op<OP>::FUSED) Op<OP>::store_fused(p, idx, v);
-                    else               Op<OP>::finish(p, idx, ex[u], v);
+                    if (Op<OP>::FUSED) Op<OP>::store_fused(p, idx, v[u]);
+                    else               Op<OP>::finish(p, idx, ex[u], v[u]);
                 }
             }
         }
