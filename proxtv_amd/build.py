@@ -38,8 +38,10 @@ def units():
     """(object name, source file, extra flags), the heaviest first so that the pool's tail is short."""
     out = []
     for op, w in SWEEP_UNITS:
-        out.append((f"sweep_unit_{op[3:].lower()}_{'w' if w else 'u'}", "sweep_unit",
-                    [f"-DPTV_UNIT_OP={op}", f"-DPTV_UNIT_W={'true' if w else 'false'}"]))
+        flags = [f"-DPTV_UNIT_OP={op}", f"-DPTV_UNIT_W={'true' if w else 'false'}"]
+        if op == "OP_DR_ROW":   # the first iteration's row sweep rides in the same object (sweep_unit.hip)
+            flags.append("-DPTV_UNIT_OP2=OP_DR_ROW_FIRST")
+        out.append((f"sweep_unit_{op[3:].lower()}_{'w' if w else 'u'}", "sweep_unit", flags))
     out += [(u, u, []) for u in PLAIN_UNITS]
     return out
 

@@ -38,6 +38,7 @@ constexpr OptionEntry kOptionTable[] = {
     {"chunk_min_len", &Options::chunk_min_len},
     {"xlink", &Options::xlink},
     {"dr_form", &Options::dr_form},
+    {"dr_first", &Options::dr_first},
     {"tile", &Options::tile},
     {"optimistic", &Options::optimistic},
     {"certify", &Options::certify},

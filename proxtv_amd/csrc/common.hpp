@@ -55,6 +55,7 @@ struct Options {
     int dr_form = 1;          // DR2 / DR2L1W: 1 = the column sweep leaves the row sweep's input and epilogue operand (OP_DR_COL_V / OP_DR_ROW_V)
                               // when the row sweep runs on the robust 64-fibre tile (rung 1); 2 = on rung 0 too; 0 = always the
                               // reference's split (OP_DR_COL / OP_DR_ROW)
+    int dr_first = 1;         // DR2 / DR2L1W: the first row sweep reads its constant operands from a table (OP_DR_ROW_FIRST); 0 = from filled arrays
     int tile = 1;             // strided sweeps on rungs 0 and 1 (unweighted and weighted): 1 = tiles of 32 fibres x 8 chunks in 4 waves (four
                               // workgroups per CU), 0 = the 64-fibre x 8-wave tile (two)
     int optimistic = 1;       // DR solves whose every sweep will run on rung 0 (decided from the sampled statistics) launch no repair kernels behind

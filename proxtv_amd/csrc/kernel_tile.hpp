@@ -74,7 +74,15 @@ __global__ __launch_bounds__(64 * NW, SHORT ? 16 / NW : (FW < 64 ? ((WEIGHTED ? 
     if (p.gate && *p.gate == 0) return;   // uniform over the grid
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);   // (uniform over the wave: scalar)
     // fl: this lane's fibre within the tile ; ch: its chunk within the block (FW = 64: the lane and the wave)
-    const int fl = FW == 64 ? lane : (lane & (FW - 1)), ch = FW == 64 ? wave : wave * CPW + lane / FW;
+    int fl = FW == 64 ? lane : (lane & (FW - 1)), ch = FW == 64 ? wave : wave * CPW + lane / FW;
+    // LEAN (Op::LEAN on the 32-fibre tile): every block works fl and ch out again, from a copy of tid the compiler cannot see through, and
+    // takes the dirty mark's epoch likewise.  What a block derives from them -- LDS addresses of the link slots and of the rebuild's rows, the
+    // epoch as a store operand -- is then computed where it is used, instead of once above the block loop and carried through the walk, the
+    // peak of the register pressure, where seven such dwords were spilled (unweighted DR row sweep: 32 B of scratch a lane, 29 MB a 4096^2
+    // launch; its robust twin 184 -> 52 B; the weighted row tiles take the same path).  This rests on how one compiler allocates registers and
+    // nothing in the suite notices the spill coming back: after any change to this kernel or to the toolchain, read the resource remark of
+    // the OP_DR_ROW unit again (hipcc -Rpass-analysis=kernel-resource-usage: ScratchSize 0, 121 VGPRs, occupancy 4 for <3,false,false,16,4,16,false,8,false,32>).
+    constexpr bool LEAN = Op<OP>::LEAN && FW < 64 && !TRANSPOSED;
     if (plan.trace && tid == 0) {
         unsigned hwid, xcc;
         asm volatile("s_getreg_b32 %0, hwreg(HW_REG_HW_ID)" : "=s"(hwid));
@@ -204,9 +212,21 @@ __global__ __launch_bounds__(64 * NW, SHORT ? 16 / NW : (FW < 64 ? ((WEIGHTED ? 
 
     for (int kb = 0; kb < nblk; kb++) {
         const int q = q_first + kb;
+        DirtyMark dirty = plan.dirty;
+        if constexpr (LEAN) {
+            int t = tid;
+            asm volatile("" : "+v"(t), "+s"(dirty.epoch));
+            fl = t & (FW - 1);
+            ch = (t >> 6) * CPW + (t & 63) / FW;
+        }
         if (plan.ablate & 4) {
-            if (kb == 0)
-                for (int e = tid; e < ROWS * PITCH; e += 64 * NW) Yp[e] = (double)((e * 2654435761u) >> 20) * 1e-3;
+            if (kb == 0) {
+                // (the counter starts from an opaque copy of tid: the fill's per-thread constants are then worked out here, in the
+                //  ablation run alone, instead of being hoisted above the block loop, where they waited in -- spilled -- registers)
+                int e = tid;
+                asm volatile("" : "+v"(e));
+                for (; e < ROWS * PITCH; e += 64 * NW) Yp[e] = (double)((e * 2654435761u) >> 20) * 1e-3;
+            }
         } else {
             stage(q);
         }
@@ -300,7 +320,7 @@ __global__ __launch_bounds__(64 * NW, SHORT ? 16 / NW : (FW < 64 ? ((WEIGHTED ? 
                 rec.mine = kLinkBad;
                 rec.next = 0;
             }
-            if (bad) flag_chunk(failflags, j, q * NCH + ch, (len + C - 1) / C, plan.dirty, rec.failed);
+            if (bad) flag_chunk(failflags, j, q * NCH + ch, (len + C - 1) / C, dirty, rec.failed);
             // Every chunk publishes its two codes: sweep_repair_kernel proves the links between workgroups with them
             // and, for a fibre with an unproven link, finds where a repair walk may stop.
             const long slot = (long)(q * NCH + ch) * g.count + j;
@@ -308,7 +328,7 @@ __global__ __launch_bounds__(64 * NW, SHORT ? 16 / NW : (FW < 64 ? ((WEIGHTED ? 
             code_next[slot] = rec.next;
             // ... and the workgroup's last chunk, right now, what the next workgroup's first chunk must have begun with
             if (plan.xlink && kb == nblk - 1 && ch == NCH - 1)
-                xlink_publish(plan.xlink + (size_t)blockIdx.y * g.count + j, plan.dirty.epoch, rec.next);
+                xlink_publish(plan.xlink + (size_t)blockIdx.y * g.count + j, dirty.epoch, rec.next);
         }
         // (the link INTO this workgroup is checked at the very end, when the workgroup before has surely published)
         if (kb == 0 && ch == 0) {

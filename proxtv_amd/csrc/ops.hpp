@@ -44,6 +44,7 @@ enum OpId : int {
     OP_YANG,           // Z/U update of Yang's ADMM
     OP_DR_COL_V,       // reflection through B_cols, leaving the row sweep's input and its epilogue operand (see Op<OP_DR_COL_V>)
     OP_DR_ROW_V,       // row sweep of that form
+    OP_DR_ROW_FIRST,   // OP_DR_ROW of a solve's first iteration: t and s' are one constant per image, read from a table, not streamed
     OP_COUNT
 };
 
@@ -55,6 +56,7 @@ struct Ext {
 // chunk kernel keeps that operand of the block's own rows in registers and asks only for the rest (fetch_rest).
 struct NoKeep {
     static constexpr bool KEEP = false;
+    static constexpr bool LEAN = false;   // (kernel_tile.hpp: the block loop of the 32-fibre tile carries no per-thread constants through the walk)
     __device__ static __forceinline__ Ext fetch_rest(const SweepArgs &, long, double) { return Ext{0, 0}; }
 };
 
@@ -197,6 +199,11 @@ template <> struct Op<OP_DR_ROW> : InBminusA, NotFused {
 #else
     static constexpr bool KEEP = false;
 #endif
+    // with the rows it keeps this kernel stands at its 128-VGPR budget of four workgroups per CU, and what spilled were not those rows but
+    // seven dwords that do not vary from block to block (kernel_tile.hpp: LEAN).  -DPTV_NO_LEAN_ROW: as before.
+#ifndef PTV_NO_LEAN_ROW
+    static constexpr bool LEAN = true;
+#endif
     __device__ static __forceinline__ Ext fetch_rest(const SweepArgs &p, long idx, double sp) { return Ext{sp, ld_once(p.c + idx)}; }
 #ifdef PTV_EXP_NOREFETCH   // experiment only (wrong results): what would the sweep cost without the second read of s'?
     __device__ static __forceinline__ Ext fetch(const SweepArgs &p, long idx) { return Ext{0.0, p.c[idx]}; }
@@ -212,6 +219,44 @@ template <> struct Op<OP_DR_ROW> : InBminusA, NotFused {
         scale = fmax(scale, fabs(tn));
         scale = fmax(scale, fabs(t));
         scale = fmax(scale, fabs(sp));
+        return 0.5 * ((2 * tn - t) - sp);
+    }
+};
+// OP_DR_ROW in the first iteration of a solve (a = U, c = t0 per image, s0 = samples per image, o0 = t_new).  There t is the constant
+// t0 = 2 mean(U) of its image and s' = -t0 (the column sweep of a constant is analytic: solvers.hip), so neither array exists: the
+// constants come from a table of one entry per image, the image from the element index (images are contiguous slabs of s0 samples in
+// every layout a sweep sees).  y = U - s' and t = 0.5 (t0 + (s' + 2 prox(y))) in OP_DR_ROW's operation order: the same bits.  One
+// streamed operand, nothing fetched by the epilogue, so nothing to keep.  (NIN = 2: the window is staged in OP_DR_ROW's two batches.)
+template <> struct Op<OP_DR_ROW_FIRST> : NotFused, NoKeep {
+    static constexpr unsigned IN_MASK = 1, OUT_MASK = 1;   // (c is a table, not an array of the sweep's shape: never transposed)
+    static constexpr int NIN = 2;
+    __device__ static __forceinline__ double t0_of(const SweepArgs &p, long idx) {
+        long k = 0;
+        if ((double)idx >= p.s0) {   // (a batch: idx < 2^53, so the quotient is off by one at most)
+            const long n = (long)p.s0;
+            k = (long)((double)idx / p.s0);
+            if (k * n > idx) k--;
+            else if ((k + 1) * n <= idx) k++;
+        }
+        return p.c[k];
+    }
+    __device__ static __forceinline__ void fetch_in(const SweepArgs &p, long idx, double &i0, double &i1) { i0 = ld_once(p.a + idx); i1 = -t0_of(p, idx); }
+    __device__ static __forceinline__ void fetch_in_shared(const SweepArgs &p, long idx, double &i0, double &i1) { i0 = p.a[idx]; i1 = -t0_of(p, idx); }
+    __device__ static __forceinline__ double y_of(const SweepArgs &, double i0, double i1) { return i0 - i1; }
+    __device__ static __forceinline__ double load_y(const SweepArgs &p, long idx) { return p.a[idx] - (-t0_of(p, idx)); }
+    __device__ static __forceinline__ Ext fetch(const SweepArgs &p, long idx) {
+        const double t0 = t0_of(p, idx);
+        return Ext{-t0, t0};
+    }
+    __device__ static __forceinline__ void finish(const SweepArgs &p, long idx, const Ext &e, double x) {
+        const double tb = e.e0 + 2 * x;
+        st_once(p.o0 + idx, 0.5 * (e.e1 + tb));
+    }
+    __device__ static __forceinline__ double recover(const SweepArgs &p, long idx, double y, double &scale) {
+        const double tn = p.o0[idx], t = t0_of(p, idx), sp = -t;   // tn = 0.5 (t + (sp + 2 x))
+        (void)y;
+        scale = fmax(scale, fabs(tn));
+        scale = fmax(scale, fabs(t));
         return 0.5 * ((2 * tn - t) - sp);
     }
 };

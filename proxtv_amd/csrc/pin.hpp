@@ -40,7 +40,7 @@ inline bool pin_supports(OpId op, bool weighted, const FibreGeom &g, double lam)
     if (weighted)
         return op == OP_PROX || op == OP_DR_COL || op == OP_DR_COL_FINAL || op == OP_DR_ROW || op == OP_DRW_ROW_FINAL || op == OP_DR_COL_V ||
                op == OP_DR_ROW_V;
-    return op != OP_DRW_ROW_FINAL && lam > 0.0;
+    return op != OP_DRW_ROW_FINAL && op != OP_DR_ROW_FIRST && lam > 0.0;   // (the first row sweep runs on the tile rungs and below only: solvers.hip)
 }
 
 // One sweep.  Strided fibres (g.inc > 1) go through transposed copies of the operands, like launch_row_along in sweep.hip.

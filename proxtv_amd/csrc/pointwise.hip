@@ -60,6 +60,12 @@ __global__ __launch_bounds__(kThreads) void dr_fill_kernel(double *t, long n, co
     for (long i = (long)blockIdx.x * kThreads + threadIdx.x; i < n; i += (long)gridDim.x * kThreads) seg[i] = v;
 }
 
+// the value dr_fill_kernel writes with sign = 1, one per image, for the sweep that reads it from a table (ops.hpp: OP_DR_ROW_FIRST)
+__global__ __launch_bounds__(kThreads) void dr_t0_kernel(double *t0, long n, const double *sums, long segments) {
+    const long b = (long)blockIdx.x * kThreads + threadIdx.x;
+    if (b < segments) t0[b] = 1.0 * (2 * sums[b] / n);
+}
+
 // Plain 8-bytes-per-lane stream copy: the access width of every sweep kernel.  Used to calibrate the rocprofv3
 // FETCH_SIZE / WRITE_SIZE counters against a known byte count (tools/pmc_traffic.sh), nothing else.
 __global__ __launch_bounds__(kThreads) void calib_copy_kernel(const double *src, double *dst, long n) {
@@ -299,6 +305,11 @@ void sum_to(const double *a, long n, long segments, double *partials, double *ou
 void dr_fill(double *t, long n, long segments, const double *sums, double sign, hipStream_t s) {
     if (transpose_cache().active) transpose_cache().forget(t);   // a writer inside a TransposeScope: copies of t are stale
     hipLaunchKernelGGL(dr_fill_kernel, dim3(grid_for(n, 1024), (unsigned)segments), dim3(kThreads), 0, s, t, n, sums, sign);
+    PTV_HIP(hipGetLastError());
+}
+
+void dr_t0(double *t0, long n, long segments, const double *sums, hipStream_t s) {
+    hipLaunchKernelGGL(dr_t0_kernel, dim3((unsigned)((segments + kThreads - 1) / kThreads)), dim3(kThreads), 0, s, t0, n, sums, segments);
     PTV_HIP(hipGetLastError());
 }
 

@@ -73,8 +73,9 @@ void prox_fibres(const double *in, double *out, const int *ns, int nds, int dim,
 //   s = t - colprox(t) ; out = [U - ((U - s) - rowprox(U - s))] - s
 // Two launches per iteration, six array passes (R t, W s' | R s', R U, R t, W t); t ping-pongs between two
 // buffers so that the row sweep never writes an array another workgroup is still reading.
+// sums: the per-image sums of U, on the device (dr2 has them under way before it waits for the policy's probe).
 static SolveInfo dr2_run(size_t M, size_t N, size_t B, const double *unary, double W1, double W2, const double *W1m,
-                         const double *W2m, double *out, int maxit, hipStream_t s) {
+                         const double *W2m, double *out, int maxit, const double *sums, hipStream_t s) {
     SolveInfo info;
     const long n1 = (long)(M * N);
     const long n = n1 * (long)B;
@@ -87,16 +88,7 @@ static SolveInfo dr2_run(size_t M, size_t N, size_t B, const double *unary, doub
     const FibreGeom cols = fibres_along(ns, 3, 0), rows = fibres_along(ns, 3, 1);
 
     Scratch t0(sizeof(double) * n), t1(sizeof(double) * n), sp(sizeof(double) * n);
-    Scratch partials(sizeof(double) * kReduceBlocks * B), sums(sizeof(double) * B);
     double *t = t0.d(), *tn = t1.d();
-
-    {   // seed of the geometry policy: the image's edge statistics along both directions (the iterates' are close to them)
-        const int both[2] = {0, 1};
-        const double *const wts[2] = {W1m, W2m};
-        policy_probe(unary, wts, ns, 3, both, 2, s);
-    }
-    sum_to(unary, n1, (long)B, partials.d(), sums.d(), s);
-    dr_fill(t, n1, (long)B, sums.d(), 1.0, s);
 
     SweepArgs col, row;
     col.lam = W1; col.w = W1m; col.o0 = sp.d();
@@ -105,7 +97,8 @@ static SolveInfo dr2_run(size_t M, size_t N, size_t B, const double *unary, doub
     // run on transposed copies may keep them (transposed.hpp)
     TransposeScope keep_transposed;
     double row_f = -1.0;
-    const int tile_rung = options().dr_form ? strided_tile_rung(rows, W2, weighted, &row_f) : -1;
+    const int row_rung = strided_tile_rung(rows, W2, weighted, &row_f);
+    const int tile_rung = options().dr_form ? row_rung : -1;
     if (options().dr_form == 2 ? tile_rung >= 0 : (tile_rung == 1 && (!weighted || (row_f >= 0.0 && row_f < kSeedDrFormWeighted)))) {
         // The row sweep runs on the robust 64-fibre tile: the column sweep does all the pointwise work (ops.hpp, OP_DR_COL_V):
         // R t, R U, W v, W s | R v, R s, W t.  Measured on 4096^2, unit noise: the column sweep, bound by its walk there, takes
@@ -114,11 +107,12 @@ static SolveInfo dr2_run(size_t M, size_t N, size_t B, const double *unary, doub
         // 134 -> 110 for the rows), so the reference's split stays there (option dr_form = 2 forces this form on rung 0 too).
         // No array is read and written by the same sweep, so t needs no second buffer: `tn` holds s, `sp` holds v = U - s'.
         double *v = sp.d(), *sarr = tn;
+        dr_fill(t, n1, (long)B, sums, 1.0, s);
         for (int it = 0; it < maxit; it++) {
             if (it == 0) {
                 // s = t - prox(t) = 0 for the constant t, s' = -t, v = U - s'
                 FamilyTimer tm(FAM_OTHER, s);
-                dr_fill(v, n1, (long)B, sums.d(), -1.0, s);
+                dr_fill(v, n1, (long)B, sums, -1.0, s);
                 lincomb(v, unary, 1.0, v, -1.0, nullptr, 0.0, nullptr, 0.0, n, s);
                 PTV_HIP(hipMemsetAsync(sarr, 0, sizeof(double) * n, s));
             } else {
@@ -130,20 +124,35 @@ static SolveInfo dr2_run(size_t M, size_t N, size_t B, const double *unary, doub
         }
         col.b = nullptr; col.o0 = sp.d(); col.o1 = nullptr;
         row.a = sp.d(); row.b = unary;
-    } else
-    for (int it = 0; it < maxit; it++) {
-        col.a = t;
-        if (it == 0) {
-            // t is constant per image, and the prox of a constant fibre is that constant: s = t - prox(t) = 0,
-            // s' = 2 s - t = -t.  (One flat piece per fibre is also the worst case for any taut-string walk.)
-            FamilyTimer tm(FAM_OTHER, s);
-            dr_fill(sp.d(), n1, (long)B, sums.d(), -1.0, s);
-        } else {
-            launch_sweep(OP_DR_COL, weighted, col, cols, s, FAM_COL, true);
+    } else {
+        // The first iteration: t is constant per image, and the prox of a constant fibre is that constant: s = t - prox(t) = 0,
+        // s' = 2 s - t = -t.  (One flat piece per fibre is also the worst case for any taut-string walk.)  Where the row sweep runs on a
+        // tile rung or below (short fibres) it reads the two constants from a table of one entry per image (ops.hpp: OP_DR_ROW_FIRST),
+        // and neither t nor s' is filled and streamed back: 536 MB and two launches less on 4096^2.  On the other rungs (transposed
+        // copies, the pinning solver), and with option dr_first = 0, the arrays are filled as before.  Same bits either way.
+        const bool first = options().dr_first && rows.inc != 1 && (rows.len < options().chunk_min_len || row_rung >= 0);
+        Scratch t0s(sizeof(double) * (first ? B : 1));
+        if (first) dr_t0(t0s.d(), n1, (long)B, sums, s);
+        else       dr_fill(t, n1, (long)B, sums, 1.0, s);
+        for (int it = 0; it < maxit; it++) {
+            col.a = t;
+            if (it == 0 && first) {
+                SweepArgs row1;
+                row1.lam = W2; row1.w = W2m; row1.a = unary; row1.c = t0s.d(); row1.s0 = (double)n1; row1.o0 = tn;
+                launch_sweep(OP_DR_ROW_FIRST, weighted, row1, rows, s, FAM_ROW, true);
+                std::swap(t, tn);
+                continue;
+            }
+            if (it == 0) {
+                FamilyTimer tm(FAM_OTHER, s);
+                dr_fill(sp.d(), n1, (long)B, sums, -1.0, s);
+            } else {
+                launch_sweep(OP_DR_COL, weighted, col, cols, s, FAM_COL, true);
+            }
+            row.c = t; row.o0 = tn;
+            launch_sweep(OP_DR_ROW, weighted, row, rows, s, FAM_ROW, true);
+            std::swap(t, tn);
         }
-        row.c = t; row.o0 = tn;
-        launch_sweep(OP_DR_ROW, weighted, row, rows, s, FAM_ROW, true);
-        std::swap(t, tn);
     }
     col.a = t;
     launch_sweep(OP_DR_COL_FINAL, weighted, col, cols, s, FAM_COL, true);
@@ -158,9 +167,13 @@ static SolveInfo dr2_run(size_t M, size_t N, size_t B, const double *unary, doub
 // themselves are the same kernels on the same data).
 SolveInfo dr2(size_t M, size_t N, size_t B, const double *unary, double W1, double W2, const double *W1m,
               const double *W2m, double *out, int maxit, hipStream_t s) {
-    if (M * N * B == 0) return dr2_run(M, N, B, unary, W1, W2, W1m, W2m, out, maxit, s);
+    if (M * N * B == 0) return dr2_run(M, N, B, unary, W1, W2, W1m, W2m, out, maxit, nullptr, s);   // (empty: returns before the sums are read)
     const int ns[3] = {(int)M, (int)N, (int)B};
-    {   // (the seed of the policy: dr2_run finds it taken)
+    // t0 = 2 mean(U) per image.  The sums do not depend on the policy's probe, whose read-back the host waits for: enqueued ahead of
+    // it, this pass over U runs during that wait and not after it.  Both runs of an optimistic solve share them.
+    Scratch partials(sizeof(double) * kReduceBlocks * B), sums(sizeof(double) * B);
+    sum_to(unary, (long)(M * N), (long)B, partials.d(), sums.d(), s);
+    {   // seed of the geometry policy: the image's edge statistics along both directions (the iterates' are close to them)
         const int both[2] = {0, 1};
         const double *const wts[2] = {W1m, W2m};
         policy_probe(unary, wts, ns, 3, both, 2, s);
@@ -169,11 +182,11 @@ SolveInfo dr2(size_t M, size_t N, size_t B, const double *unary, double W1, doub
     const double lams[2] = {W1, W2};
     OptimisticScope opt(s, optimistic_eligible(geoms, lams, 2, W1m != nullptr));
     const bool tried = opt.on;
-    SolveInfo info = dr2_run(M, N, B, unary, W1, W2, W1m, W2m, out, maxit, s);
+    SolveInfo info = dr2_run(M, N, B, unary, W1, W2, W1m, W2m, out, maxit, sums.d(), s);
     if (tried) count_event(CNT_OPTIMISTIC_SOLVES);
     if (!opt.clean()) {
         count_event(CNT_OPTIMISTIC_REDONE);
-        info = dr2_run(M, N, B, unary, W1, W2, W1m, W2m, out, maxit, s);
+        info = dr2_run(M, N, B, unary, W1, W2, W1m, W2m, out, maxit, sums.d(), s);
     }
     return info;
 }

@@ -232,6 +232,7 @@ void launch_seq_gated(OpId op, bool weighted, const SweepArgs &args, const Fibre
 #define PTV_GATED(ID, W) \
     if (op == ID && weighted == W) return unit_gated<ID, W>(args, g, stream, flags);
     PTV_SWEEP_UNITS(PTV_GATED)
+    PTV_GATED(OP_DR_ROW_FIRST, false) PTV_GATED(OP_DR_ROW_FIRST, true)
 #undef PTV_GATED
     set_error("launch_seq_gated: no %s sweep for op %d", weighted ? "weighted" : "unweighted", (int)op);
     throw HipFailure{hipErrorInvalidValue};
@@ -249,6 +250,7 @@ void launch_sweep(OpId op, bool weighted, const SweepArgs &args, const FibreGeom
 #define PTV_CASE(ID, W) \
     if (op == ID && weighted == W) return unit_launch<ID, W>(args, g, stream, allow_chunked, fam);
     PTV_SWEEP_UNITS(PTV_CASE)
+    PTV_CASE(OP_DR_ROW_FIRST, false) PTV_CASE(OP_DR_ROW_FIRST, true)
 #undef PTV_CASE
     set_error("launch_sweep: no %s sweep for op %d", weighted ? "weighted" : "unweighted", (int)op);
     throw HipFailure{hipErrorInvalidValue};
@@ -259,6 +261,7 @@ long certify_sweep(OpId op, bool weighted, const SweepArgs &args, const FibreGeo
 #define PTV_CERT(ID, W) \
     if (op == ID && weighted == W) return unit_certify<ID, W>(args, g, stream);
     PTV_SWEEP_UNITS(PTV_CERT)
+    PTV_CERT(OP_DR_ROW_FIRST, false) PTV_CERT(OP_DR_ROW_FIRST, true)
 #undef PTV_CERT
     set_error("certify_sweep: no %s sweep for op %d", weighted ? "weighted" : "unweighted", (int)op);
     throw HipFailure{hipErrorInvalidValue};

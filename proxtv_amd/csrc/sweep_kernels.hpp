@@ -56,6 +56,9 @@ template <int OP, bool WEIGHTED> long unit_certify(const SweepArgs &args, const 
     template <> void unit_warm<ID, W>();                                                                                     \
     template <> long unit_certify<ID, W>(const SweepArgs &args, const FibreGeom &g, hipStream_t stream);
 PTV_SWEEP_UNITS(PTV_DECLARE_UNIT)
+// (rides in the two OP_DR_ROW units -- sweep_unit.hip: PTV_UNIT_OP2 --: one launch a solve does not earn objects of its own)
+PTV_DECLARE_UNIT(OP_DR_ROW_FIRST, false)
+PTV_DECLARE_UNIT(OP_DR_ROW_FIRST, true)
 #undef PTV_DECLARE_UNIT
 }  // namespace swp
 
