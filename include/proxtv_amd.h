@@ -300,6 +300,42 @@ int proxtv_PD_TV_vjp_dev(int which /*0: PD2_TV, 1: PD_TV*/, const double *y, con
                          double *x /*forward result, or NULL*/, double *gy /*may be g*/, double *glam /*host double[npen], or NULL*/,
                          void *stream);
 
+/* Step codes: all that the three derivatives above read of a sweep output y, at 2 bits a sample instead of 64.  One 32-bit word per
+   chunk of 16 consecutive samples of a fibre (the last chunk of a fibre may be short):
+     bit k      (k < 16)   the edge behind sample k of the chunk -- between it and the fibre's next sample -- is a STEP (the rule above)
+     bit 16 + k            that step goes up (y[k+1] > y[k])
+   and every bit of an edge the chunk does not own is 0: beyond a short last chunk, and behind the fibre's last sample.  So
+   popcount(word & 0xffff) summed over a fibre is its segments less one, and (word >> 16) & ~word & 0xffff is 0.  The bit format is
+   public; the ORDER of the words is the library's own (it follows the layout of the kernels' scratch records, so it depends on ns and
+   dim) and holds for the same ns and dim on the same build.  A derivative computed from the words is the same bits as the one computed
+   from y: the kernels take nothing else from y.
+   proxtv_tv1_steps_words: how many words an array has along `dim`: (fibres) * ceil(ns[dim] / 16); 0 for an empty array; -1 with
+   proxtv_last_error set for a dimension out of range.  Needs no device.
+   proxtv_tv1_fibres_steps_dev: steps[proxtv_tv1_steps_words(...)] <- the codes of y.  One pass over y, no atomics: the same words every
+   call.  steps must not overlap y.  Synchronises the stream; returns 1, or 0 with proxtv_last_error set.
+   proxtv_tv1_fibres_vjp_steps_dev: proxtv_tv1_fibres_vjp_dev with those words in place of y -- the same arguments, rules and results
+   (gx may be g; ns[dim] == 1: gx = g; gx == NULL: nseg alone, read off the words). */
+long proxtv_tv1_steps_words(const int *ns /*host*/, int nds, int dim);
+int proxtv_tv1_fibres_steps_dev(const double *y, unsigned *steps, const int *ns /*host*/, int nds, int dim, void *stream);
+int proxtv_tv1_fibres_vjp_steps_dev(const unsigned *steps, const double *g, double *gx /*or NULL*/, double *gw /*or NULL*/,
+                                    int *nseg /*or NULL*/, const int *ns /*host*/, int nds, int dim, void *stream);
+
+/* proxtv_DR2_TV_vjp_dev / proxtv_PD_TV_vjp_dev with the choice of what the forward keeps for the reverse sweeps:
+     tape = 0   every sweep output, as float64: the two calls above, bit for bit
+     tape = 1   the step codes of every sweep output: each sweep writes into an array that the next iteration reuses (two arrays for
+                Douglas-Rachford and PD2, npen for PD) and is encoded behind its sweep.  What is kept, and what is held against the
+                pool's cap, is 4 bytes per 16 samples and sweep plus those arrays: for Douglas-Rachford
+                (maxit + 1) * 4 * (words along dimension 0 + words along dimension 1) + 2 * 8 * M * N * B bytes.
+   Every result is the same bits for both tapes.  Any other value of `tape`: returns 0 with proxtv_last_error set and nothing written.
+   All else as documented above. */
+int proxtv_DR2_TV_vjp_tape_dev(size_t M, size_t N, size_t B, const double *unary, double W1, double W2, const double *W1m /*or NULL*/,
+                               const double *W2m /*or NULL*/, const double *g, double *s /*or NULL*/, double *gU, double *gW1 /*or NULL*/,
+                               double *gW2 /*or NULL*/, double *glam /*host, or NULL*/, int maxit, int tape, void *stream);
+int proxtv_PD_TV_vjp_tape_dev(int which /*0: PD2_TV, 1: PD_TV*/, const double *y, const double *lambdas /*host*/,
+                              const double *dims /*host, 1-based*/, const int *ns /*host*/, int nds, int npen, int iters, const double *g,
+                              double *x /*forward result, or NULL*/, double *gy /*may be g*/, double *glam /*host double[npen], or NULL*/,
+                              int tape, void *stream);
+
 /* Batch of B independent MxN images stored back to back (image b at unary + b*M*N), each solved
    with DR2_TV semantics (oracle = loop of DR2_TV).  All B images advance together, one
    launch per sweep over B*N (columns) / B*M (rows) fibres. */

@@ -15,6 +15,10 @@ ONE device.tvgen_vjp call with the iteration count the forward reported (DESIGN.
 differentiated: compose them from tv1_fibres and torch's pointwise operations.
 
     y = autograd.tvgen(x, [w0, w1, w2], [1, 2, 3])   # a volume; every w a float or a 0-d float64 tensor
+
+Every function takes ``tape="outputs"`` (the default) or ``tape="steps"``: what is kept for the reverse sweeps.  With "steps",
+tv1_fibres saves the 2-bit step codes of its output (device.tv1_fibres_steps: an int32 tensor of 1/32 of y's bytes) in the graph instead
+of y, and the solver derivatives keep step codes instead of their sweep outputs while they run.  Every gradient is the same bits.
 """
 import torch
 
@@ -23,10 +27,10 @@ from . import device
 
 class _TV1Fibres(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, x, w, weights, dim):
+    def forward(ctx, x, w, weights, dim, tape):
         y = device.tv1_fibres(_colmajor(x.detach()), float(w), dim, None if weights is None else _colmajor(weights.detach()))
-        ctx.save_for_backward(y)
-        ctx.dim = dim
+        ctx.save_for_backward(device.tv1_fibres_steps(y, dim) if tape == "steps" else y)
+        ctx.dim, ctx.tape, ctx.shape = dim, tape, tuple(y.shape)
         ctx.w_device = w.device if isinstance(w, torch.Tensor) else None
         ctx.weighted = weights is not None
         return y
@@ -36,34 +40,38 @@ class _TV1Fibres(torch.autograd.Function):
     def backward(ctx, gy):
         (y,) = ctx.saved_tensors
         need_x, need_w, need_weights = ctx.needs_input_grad[:3]
-        gx, gw, _ = device.tv1_fibres_vjp(y, gy, ctx.dim, need_gw=need_w or need_weights)
+        if ctx.tape == "steps":     # (y is the word tensor)
+            gx, gw, _ = device.tv1_fibres_vjp_steps(y, gy, ctx.shape, ctx.dim, need_gw=need_w or need_weights)
+        else:
+            gx, gw, _ = device.tv1_fibres_vjp(y, gy, ctx.dim, need_gw=need_w or need_weights)
         gw_scalar = None
         if need_w:
             # (with per-edge weights the scalar w does not enter the prox: its gradient is zero)
             gw_scalar = (torch.zeros((), dtype=torch.float64) if ctx.weighted else gw.sum()).to(ctx.w_device)
-        return (gx if need_x else None), gw_scalar, (gw if need_weights else None), None
+        return (gx if need_x else None), gw_scalar, (gw if need_weights else None), None, None
 
 
 def _colmajor(t):
     return t if device._is_colmajor(t) else device.to_colmajor(t)
 
 
-def tv1_fibres(x, w, dim, weights=None):
+def tv1_fibres(x, w, dim, weights=None, tape="outputs"):
     """``device.tv1_fibres(x, w, dim, weights)`` with a graph behind it: differentiable in x, in `weights`, and in w when w is a 0-d
     float64 tensor (its gradient comes back on that tensor's device).  When nothing asks for a gradient this IS device.tv1_fibres."""
     if isinstance(w, torch.Tensor) and (w.dim() != 0 or w.dtype != torch.float64):
         raise ValueError("w: expected a float or a 0-d float64 tensor")
+    device._tape(tape)
     wants = torch.is_grad_enabled() and any(isinstance(t, torch.Tensor) and t.requires_grad for t in (x, w, weights))
     if not wants:
         return device.tv1_fibres(x, float(w), dim, weights)
-    return _TV1Fibres.apply(x, w, weights, int(dim))
+    return _TV1Fibres.apply(x, w, weights, int(dim), tape)
 
 
 class _DR2(torch.autograd.Function):
     """x, then the two penalties: 0-d tensors / floats (uniform) or the two per-edge maps (`weighted`)."""
 
     @staticmethod
-    def forward(ctx, x, p_col, p_row, max_iters, weighted):
+    def forward(ctx, x, p_col, p_row, max_iters, weighted, tape):
         xd = _colmajor(x.detach())
         if weighted:
             wc, wr = _colmajor(p_col.detach()), _colmajor(p_row.detach())
@@ -77,7 +85,7 @@ class _DR2(torch.autograd.Function):
             ctx.save_for_backward(xd)
             ctx.lams = (float(p_col), float(p_row))
             ctx.lam_devices = tuple(p.device if isinstance(p, torch.Tensor) else None for p in (p_col, p_row))
-        ctx.max_iters, ctx.weighted = max_iters, weighted
+        ctx.max_iters, ctx.weighted, ctx.tape = max_iters, weighted, tape
         return y
 
     @staticmethod
@@ -87,15 +95,16 @@ class _DR2(torch.autograd.Function):
         if ctx.weighted:
             x, wc, wr = ctx.saved_tensors
             gx, gc, gr, _, _ = device.dr2_vjp(x, gy, 0.0, max_iters=ctx.max_iters, weights_col=wc, weights_row=wr,
-                                              need_gw=need_col or need_row)
+                                              need_gw=need_col or need_row, tape=ctx.tape)
         else:
             (x,) = ctx.saved_tensors
-            gx, _, _, glam, _ = device.dr2_vjp(x, gy, ctx.lams[0], ctx.lams[1], ctx.max_iters, need_gw="sums" if need_col or need_row else False)
+            gx, _, _, glam, _ = device.dr2_vjp(x, gy, ctx.lams[0], ctx.lams[1], ctx.max_iters, need_gw="sums" if need_col or need_row else False,
+                                               tape=ctx.tape)
             gc = gr = None
             if glam is not None:
                 glam = glam.reshape(-1, 2).sum(axis=0)     # (a batch shares its penalties)
                 gc, gr = (None if d is None else torch.tensor(v, dtype=torch.float64, device=d) for v, d in zip(glam, ctx.lam_devices))
-        return (gx if need_x else None), (gc if need_col else None), (gr if need_row else None), None, None
+        return (gx if need_x else None), (gc if need_col else None), (gr if need_row else None), None, None, None
 
 
 def _scalar_penalty(w, name):
@@ -107,44 +116,47 @@ def _wants(*ts):
     return torch.is_grad_enabled() and any(isinstance(t, torch.Tensor) and t.requires_grad for t in ts)
 
 
-def tv1_2d(x, w, max_iters=0, w_row=None):
+def tv1_2d(x, w, max_iters=0, w_row=None, tape="outputs"):
     """``device.tv1_2d(x, w, max_iters, w_row=w_row)[0]`` (the Douglas-Rachford solve) with a graph behind it: differentiable in x and in
     w / w_row where they are 0-d float64 tensors (the gradient comes back on that tensor's device; one tensor for both directions
     receives the sum).  The result is bit for bit device.tv1_2d's; when nothing asks for a gradient this IS device.tv1_2d."""
     _scalar_penalty(w, "w")
     _scalar_penalty(w_row, "w_row")
+    device._tape(tape)
     if not _wants(x, w, w_row):
         return device.tv1_2d(x, float(w), max_iters, w_row=None if w_row is None else float(w_row))[0]
-    return _DR2.apply(x, w, w if w_row is None else w_row, int(max_iters), False)
+    return _DR2.apply(x, w, w if w_row is None else w_row, int(max_iters), False, tape)
 
 
-def tv1w_2d(x, w_col, w_row, max_iters=0):
+def tv1w_2d(x, w_col, w_row, max_iters=0, tape="outputs"):
     """``device.tv1w_2d(x, w_col, w_row, max_iters)[0]`` with a graph behind it: differentiable in x and in both weight maps."""
+    device._tape(tape)
     if not _wants(x, w_col, w_row):
         return device.tv1w_2d(x, w_col, w_row, max_iters)[0]
-    return _DR2.apply(x, w_col, w_row, int(max_iters), True)
+    return _DR2.apply(x, w_col, w_row, int(max_iters), True, tape)
 
 
-def tv1_2d_batch(xs, w, max_iters=0):
+def tv1_2d_batch(xs, w, max_iters=0, tape="outputs"):
     """``device.tv1_2d_batch(xs, w, max_iters)[0]`` on an (M, N, B) stack with a graph behind it: differentiable in xs and in a 0-d
     float64 tensor w (the sum over the images and both directions)."""
     _scalar_penalty(w, "w")
+    device._tape(tape)
     if not _wants(xs, w):
         return device.tv1_2d_batch(xs, float(w), max_iters)[0]
-    return _DR2.apply(xs, w, w, int(max_iters), False)
+    return _DR2.apply(xs, w, w, int(max_iters), False, tape)
 
 
 class _TVGen(torch.autograd.Function):
-    """x, then the penalties one by one (0-d tensors / floats); ds, max_iters and method ride in `spec`."""
+    """x, then the penalties one by one (0-d tensors / floats); ds, max_iters, method and tape ride in `spec`."""
 
     @staticmethod
     def forward(ctx, x, spec, *ws):
-        ds, max_iters, method = spec
+        ds, max_iters, method, tape = spec
         xd = _colmajor(x.detach())
         lams = [float(w) for w in ws]
         y, info = device.tvgen(xd, lams, ds, max_iters, method)
         ctx.save_for_backward(xd)
-        ctx.lams, ctx.ds, ctx.method = lams, ds, method
+        ctx.lams, ctx.ds, ctx.method, ctx.tape = lams, ds, method, tape
         ctx.iters = int(info[0])
         ctx.lam_devices = tuple(w.device if isinstance(w, torch.Tensor) else None for w in ws)
         return y
@@ -157,13 +169,13 @@ class _TVGen(torch.autograd.Function):
         if x.numel() == 0 or ctx.iters < 1:      # (nothing was iterated: the result does not depend on anything)
             gx, glam = torch.zeros_like(x), [0.0] * len(ctx.lams)
         else:
-            gx, glam, _ = device.tvgen_vjp(x, gy, ctx.lams, ctx.ds, ctx.iters, ctx.method, need_glam=any(need_ws))
+            gx, glam, _ = device.tvgen_vjp(x, gy, ctx.lams, ctx.ds, ctx.iters, ctx.method, need_glam=any(need_ws), tape=ctx.tape)
         gws = tuple(torch.tensor(float(glam[i]), dtype=torch.float64, device=ctx.lam_devices[i]) if need else None
                     for i, need in enumerate(need_ws))
         return ((gx if need_x else None), None) + gws
 
 
-def tvgen(x, ws, ds, max_iters=0, method=None):
+def tvgen(x, ws, ds, max_iters=0, method=None, tape="outputs"):
     """``device.tvgen(x, ws, ds, max_iters, method)[0]`` with a graph behind it: differentiable in x and in every entry of `ws` that is a
     0-d float64 tensor (its gradient comes back on that tensor's device; a tensor that appears in several entries receives the sum).
     method: None (tvgen's dispatch), 'pd2' or 'pd'; 'pdr' and 'yang' raise NotImplementedError when a gradient is asked for.  The result
@@ -172,9 +184,10 @@ def tvgen(x, ws, ds, max_iters=0, method=None):
     ws = list(ws)
     for i, w in enumerate(ws):
         _scalar_penalty(w, f"ws[{i}]")
+    device._tape(tape)
     if not _wants(x, *ws):
         return device.tvgen(x, [float(w) for w in ws], ds, max_iters, method)[0]
     m = method if method is not None else ("pd2" if len(ws) == 2 else "pd")
     if m not in ("pd2", "pd"):
         raise NotImplementedError(f"method {m!r} has no derivative (autograd.tvgen covers 'pd2' and 'pd')")
-    return _TVGen.apply(x, (tuple(float(d) for d in ds), int(max_iters), method), *ws)
+    return _TVGen.apply(x, (tuple(float(d) for d in ds), int(max_iters), method, tape), *ws)

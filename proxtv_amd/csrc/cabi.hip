@@ -680,9 +680,60 @@ int proxtv_tv1_fibres_vjp_dev(const double *y, const double *g, double *gx, doub
     });
 }
 
-int proxtv_DR2_TV_vjp_dev(size_t M, size_t N, size_t B, const double *unary, double W1, double W2, const double *W1m, const double *W2m,
-                          const double *g, double *s, double *gU, double *gW1, double *gW2, double *glam, int maxit, void *stream) {
-    return guarded("proxtv_DR2_TV_vjp_dev", nullptr, 1, [&] {
+long proxtv_tv1_steps_words(const int *ns, int nds, int dim) {
+    set_error("");
+    if (!ns || dim < 0 || dim >= nds) {
+        set_error("dimension out of range");
+        return -1;
+    }
+    return tv1_steps_words(ns, nds, dim);
+}
+
+int proxtv_tv1_fibres_steps_dev(const double *y, unsigned *steps, const int *ns, int nds, int dim, void *stream) {
+    return guarded("proxtv_tv1_fibres_steps_dev", nullptr, 1, [&] {
+        if (dim < 0 || dim >= nds) reject("dimension out of range");
+        const size_t n = (size_t)total(ns, nds), nw = (size_t)tv1_steps_words(ns, nds, dim);
+        if (n == 0) return;
+        if (!y || !steps) reject("y and steps are required");
+        const char *y0 = reinterpret_cast<const char *>(y), *w0 = reinterpret_cast<const char *>(steps);
+        if (y0 < w0 + sizeof(unsigned) * nw && w0 < y0 + sizeof(double) * n) reject("steps overlaps y");
+        tv1_fibres_steps(y, steps, ns, nds, dim, pick(stream));
+    });
+}
+
+int proxtv_tv1_fibres_vjp_steps_dev(const unsigned *steps, const double *g, double *gx, double *gw, int *nseg, const int *ns, int nds, int dim,
+                                    void *stream) {
+    return guarded("proxtv_tv1_fibres_vjp_steps_dev", nullptr, 1, [&] {
+        if (dim < 0 || dim >= nds) reject("dimension out of range");
+        const size_t n = (size_t)total(ns, nds);
+        if (n == 0) return;
+        if (!steps) reject("steps is required");
+        hipStream_t st = pick(stream);
+        if (!gx) {   // the segment counts alone
+            tv1_fibres_vjp_steps(steps, nullptr, nullptr, nullptr, nseg, ns, nds, dim, st);
+            return;
+        }
+        if (!g) reject("g is required when gx is asked for");
+        const size_t nw = (gw && ns[dim] > 1) ? n / (size_t)ns[dim] * (size_t)(ns[dim] - 1) : 0;
+        // (the words, counted in doubles for the overlap test)
+        const double *sd = reinterpret_cast<const double *>(steps);
+        const size_t ns8 = ((size_t)tv1_steps_words(ns, nds, dim) * sizeof(unsigned) + sizeof(double) - 1) / sizeof(double);
+        // gx == g is served in place (vjp.hip); any other overlap goes through scratch like everywhere else
+        OutGuard ox(gx, n, {{sd, ns8}, {gx == g ? nullptr : g, n}, {gw, nw}});
+        OutGuard ow(nw ? gw : nullptr, nw, {{sd, ns8}, {g, n}});
+        tv1_fibres_vjp_steps(steps, g, ox.ptr(), ow.ptr(), nseg, ns, nds, dim, st);
+        ox.commit(st);
+        ow.commit(st);
+        PTV_HIP(hipStreamSynchronize(st));
+    });
+}
+
+// proxtv_DR2_TV_vjp_dev is the tape = 0 call of proxtv_DR2_TV_vjp_tape_dev
+static int dr2_vjp_entry(const char *who, size_t M, size_t N, size_t B, const double *unary, double W1, double W2, const double *W1m,
+                         const double *W2m, const double *g, double *s, double *gU, double *gW1, double *gW2, double *glam, int maxit, int tape,
+                         void *stream) {
+    return guarded(who, nullptr, 1, [&] {
+        if (tape != 0 && tape != 1) reject("tape: 0 (sweep outputs) or 1 (step codes)");
         const size_t n = M * N * B;
         if (n == 0) return;
         if (M > 0x7fffffffu || N > 0x7fffffffu || B > 65535u) reject("image extents beyond 2^31 - 1 or more than 65535 images");
@@ -704,21 +755,34 @@ int proxtv_DR2_TV_vjp_dev(size_t M, size_t N, size_t B, const double *unary, dou
                 }
             }
         }
-        const size_t tape = dr2_vjp_tape_bytes(M, N, B, maxit);
-        if (tape > pool_cap_bytes()) {
-            set_error("the tape of sweep outputs needs %zu bytes, the scratch pool is capped at %zu (PROXTV_POOL_CAP_MB)", tape, pool_cap_bytes());
+        const size_t need = dr2_vjp_tape_bytes(M, N, B, maxit, tape);
+        if (need > pool_cap_bytes()) {
+            set_error("the tape of sweep outputs needs %zu bytes, the scratch pool is capped at %zu (PROXTV_POOL_CAP_MB)", need, pool_cap_bytes());
             throw HipFailure{hipErrorOutOfMemory};
         }
         hipStream_t st = pick(stream);
         SolveScope scope(st);
-        dr2_vjp(M, N, B, unary, W1, W2, W1m, W2m, g, s, gU, gW1, gW2, glam, maxit, st);
+        dr2_vjp(M, N, B, unary, W1, W2, W1m, W2m, g, s, gU, gW1, gW2, glam, maxit, tape, st);
         scope.finish();
     });
 }
 
-int proxtv_PD_TV_vjp_dev(int which, const double *y, const double *lambdas, const double *dims, const int *ns, int nds, int npen, int iters,
-                         const double *g, double *x, double *gy, double *glam, void *stream) {
-    return guarded("proxtv_PD_TV_vjp_dev", nullptr, 1, [&] {
+int proxtv_DR2_TV_vjp_dev(size_t M, size_t N, size_t B, const double *unary, double W1, double W2, const double *W1m, const double *W2m,
+                          const double *g, double *s, double *gU, double *gW1, double *gW2, double *glam, int maxit, void *stream) {
+    return dr2_vjp_entry("proxtv_DR2_TV_vjp_dev", M, N, B, unary, W1, W2, W1m, W2m, g, s, gU, gW1, gW2, glam, maxit, 0, stream);
+}
+
+int proxtv_DR2_TV_vjp_tape_dev(size_t M, size_t N, size_t B, const double *unary, double W1, double W2, const double *W1m, const double *W2m,
+                               const double *g, double *s, double *gU, double *gW1, double *gW2, double *glam, int maxit, int tape,
+                               void *stream) {
+    return dr2_vjp_entry("proxtv_DR2_TV_vjp_tape_dev", M, N, B, unary, W1, W2, W1m, W2m, g, s, gU, gW1, gW2, glam, maxit, tape, stream);
+}
+
+// proxtv_PD_TV_vjp_dev is the tape = 0 call of proxtv_PD_TV_vjp_tape_dev
+static int pd_vjp_entry(const char *who, int which, const double *y, const double *lambdas, const double *dims, const int *ns, int nds, int npen,
+                        int iters, const double *g, double *x, double *gy, double *glam, int tape, void *stream) {
+    return guarded(who, nullptr, 1, [&] {
+        if (tape != 0 && tape != 1) reject("tape: 0 (sweep outputs) or 1 (step codes)");
         if (which != 0 && which != 1) reject("which: 0 (PD2_TV) or 1 (PD_TV)");
         if (iters < 1) reject("iters: the iteration count of the forward solve (info[0]), at least 1");
         if (npen < 1) reject("at least one penalty term is required");
@@ -741,16 +805,26 @@ int proxtv_PD_TV_vjp_dev(int which, const double *y, const double *lambdas, cons
                 }
             }
         }
-        const size_t tape = pd_vjp_tape_bytes(which, ns, nds, npen, iters);
-        if (tape > pool_cap_bytes()) {
-            set_error("the tape of sweep outputs needs %zu bytes, the scratch pool is capped at %zu (PROXTV_POOL_CAP_MB)", tape, pool_cap_bytes());
+        const size_t need = pd_vjp_tape_bytes(which, dims, ns, nds, npen, iters, tape);
+        if (need > pool_cap_bytes()) {
+            set_error("the tape of sweep outputs needs %zu bytes, the scratch pool is capped at %zu (PROXTV_POOL_CAP_MB)", need, pool_cap_bytes());
             throw HipFailure{hipErrorOutOfMemory};
         }
         hipStream_t st = pick(stream);
         SolveScope scope(st);
-        pd_vjp(which, y, lambdas, dims, ns, nds, npen, iters, g, x, gy, glam, st);
+        pd_vjp(which, y, lambdas, dims, ns, nds, npen, iters, g, x, gy, glam, tape, st);
         scope.finish();
     });
+}
+
+int proxtv_PD_TV_vjp_dev(int which, const double *y, const double *lambdas, const double *dims, const int *ns, int nds, int npen, int iters,
+                         const double *g, double *x, double *gy, double *glam, void *stream) {
+    return pd_vjp_entry("proxtv_PD_TV_vjp_dev", which, y, lambdas, dims, ns, nds, npen, iters, g, x, gy, glam, 0, stream);
+}
+
+int proxtv_PD_TV_vjp_tape_dev(int which, const double *y, const double *lambdas, const double *dims, const int *ns, int nds, int npen, int iters,
+                              const double *g, double *x, double *gy, double *glam, int tape, void *stream) {
+    return pd_vjp_entry("proxtv_PD_TV_vjp_tape_dev", which, y, lambdas, dims, ns, nds, npen, iters, g, x, gy, glam, tape, stream);
 }
 
 int proxtv_tvp_fibres_dev(const double *in, double *out, const int *ns, int nds, int dim, double lambda, double p,

@@ -24,20 +24,29 @@ long certify_fibres(const double *in, const double *out, const int *ns, int nds,
 void tv1_fibres_vjp(const double *y, const double *g, double *gx, double *gw, int *nseg, const int *ns, int nds, int dim,
                     hipStream_t s);
 
+// the step codes of y (vjpcore.hpp: one 32-bit word per chunk of 16 samples, all the derivative reads of y): tv1_steps_words of them, in
+// the library's own order for this ns / dim; and the derivative above from those words.  gx == null: nseg alone.  Both drain the stream.
+long tv1_steps_words(const int *ns, int nds, int dim);
+void tv1_fibres_steps(const double *y, unsigned *steps, const int *ns, int nds, int dim, hipStream_t s);
+void tv1_fibres_vjp_steps(const unsigned *steps, const double *g, double *gx, double *gw, int *nseg, const int *ns, int nds, int dim,
+                          hipStream_t s);
+
 // the derivative of dr2 (vjp.hip): runs the unfused recurrence with its 2 (maxit + 1) sweep outputs kept in pool scratch
 // (dr2_vjp_tape_bytes; the caller checks it against pool_cap_bytes), then the reverse sweeps.  out / gW1 / gW2 / glam may be null; gU may
 // be g, no other overlap.  glam: HOST double[2 B], (sum gW1, sum gW2) per image.  Returns with the stream drained.
-size_t dr2_vjp_tape_bytes(size_t M, size_t N, size_t B, int maxit);
+// tape = 1: the sweeps write into two reused arrays and only the step codes of every output are kept (32 times less per output).
+size_t dr2_vjp_tape_bytes(size_t M, size_t N, size_t B, int maxit, int tape);
 void dr2_vjp(size_t M, size_t N, size_t B, const double *unary, double W1, double W2, const double *W1m, const double *W2m, const double *g,
-             double *out, double *gU, double *gW1, double *gW2, double *glam, int maxit, hipStream_t s);
+             double *out, double *gU, double *gW1, double *gW2, double *glam, int maxit, int tape, hipStream_t s);
 
 // the derivative of pd2 (which == 0; npen <= 2) / pd (which == 1) with TV-L1 terms (vjp.hip): runs `iters` iterations of the
 // unfused recurrence -- no stopping test, nothing read back -- with every sweep output kept in pool scratch (pd_vjp_tape_bytes; the caller
 // checks it against pool_cap_bytes), then the reverse sweeps.  lambdas / dims: host, as pd2 / pd take them.  x / glam may be null; gy may be
 // g, no other overlap.  glam: HOST double[npen], the gradient in `lambdas` as passed.  Returns with the stream drained.
-size_t pd_vjp_tape_bytes(int which, const int *ns, int nds, int npen, int iters);
+// tape = 1: step codes of every output, and one reused array per term.
+size_t pd_vjp_tape_bytes(int which, const double *dims, const int *ns, int nds, int npen, int iters, int tape);
 void pd_vjp(int which, const double *y, const double *lambdas, const double *dims, const int *ns, int nds, int npen, int iters, const double *g,
-            double *x, double *gy, double *glam, hipStream_t s);
+            double *x, double *gy, double *glam, int tape, hipStream_t s);
 
 // out = prox along `dim` with the TV-L1 (norm 1: the sweep kernels) or TV-L2 (norm 2: tv2.hip) penalty; in != out
 void prox_fibres(const double *in, double *out, const int *ns, int nds, int dim, double lam, double norm, hipStream_t s);

@@ -10,8 +10,14 @@
 // from the pool; there are no atomics: every sum has one order, so two calls give the same bits.  An output may be its input g:
 // a chunk reads all it needs of g before anything of gx is written, and no chunk reads another's g.
 //
+// Phases A and C take of y only which edges step and which way (vjpcore.hpp: chunk_load), so both kernels have a second source, chosen
+// at compile time beside MODE: the 2-bit step codes of y, one 32-bit word per chunk (vjp_encode_*_kernel writes them, in the order of
+// the Summary / Resolved records, so a lane's word is one coalesced load).  The word instantiations load no y -- 0.25 B a sample in
+// place of 8 -- and give the same bits (proxtv_tv1_fibres_steps_dev, proxtv_tv1_fibres_vjp_steps_dev).
+//
 // The second half of the file is the derivative of the 2-D Douglas-Rachford solve (proxtv_DR2_TV_vjp_dev): the unfused
-// forward recurrence with its sweep outputs kept, then the same three phases once per sweep, last sweep first.  The pointwise work of
+// forward recurrence with its sweep outputs kept (tape = 0) or their step codes (tape = 1: the sweeps write into arrays the next
+// iteration reuses and each output is encoded behind its sweep), then the same three phases once per sweep, last sweep first.  The pointwise work of
 // the reverse recurrence rides in phase C as epilogue variants of the two kernels (VJP_DR_ROW / VJP_DR_COL below), the way ops.hpp
 // folds the forward's into the sweeps: a reverse iteration is two fibre VJPs and no other pass over the arrays.
 //
@@ -22,6 +28,7 @@
 
 #include <algorithm>
 #include <memory>
+#include <type_traits>
 #include <vector>
 
 #include "pointwise.hpp"
@@ -60,6 +67,13 @@ struct VjpEpi {
     const double *zeta = nullptr;         // VJP_PD
     double scale = 0.0;                   // VJP_PD: 1 / P
 };
+
+// what the chunk kernels read the steps from: y itself (SRC = double) or the code words vjp_encode left of it (SRC = unsigned)
+template <class SRC>
+constexpr bool vjp_from_words() {
+    static_assert(std::is_same<SRC, double>::value || std::is_same<SRC, unsigned>::value, "the source is y or its code words");
+    return std::is_same<SRC, unsigned>::value;
+}
 
 constexpr bool vjp_writes(int mode) { return mode != VJP_SUMMARY && mode != VJP_PD_SUMMARY; }
 constexpr bool vjp_forms_cotangent(int mode) { return mode == VJP_PD_SUMMARY || mode == VJP_PD; }
@@ -108,11 +122,11 @@ __device__ __forceinline__ void vjp_store_gw(const VjpEpi &e, double *gw, long i
 }
 
 // ---- strided fibres: wave = 64 adjacent fibres x one chunk ---------------------------------------------------------------------
-// S and R are indexed chunk * count + fibre (adjacent lanes, adjacent records)
-template <int MODE>
-__global__ __launch_bounds__(256) void vjp_strided_kernel(const double *y, const double *g, double *gx, double *gw, FibreGeom geo, int nch,
+// S and R are indexed chunk * count + fibre (adjacent lanes, adjacent records), and so are the code words when y is those
+template <int MODE, class SRC>
+__global__ __launch_bounds__(256) void vjp_strided_kernel(const SRC *y, const double *g, double *gx, double *gw, FibreGeom geo, int nch,
                                                           Summary *S, const Resolved *R, VjpEpi epi) {
-    constexpr bool WRITE = vjp_writes(MODE), KEEP = vjp_keeps(MODE);
+    constexpr bool WRITE = vjp_writes(MODE), KEEP = vjp_keeps(MODE), WORDS = vjp_from_words<SRC>();
     const long unit = (long)blockIdx.x * 4 + (threadIdx.x >> 6), groups = (geo.count + 63) / 64;
     if (unit >= groups * nch) return;
     long grp, c;
@@ -124,17 +138,23 @@ __global__ __launch_bounds__(256) void vjp_strided_kernel(const double *y, const
     const int k0 = (int)c * kVjpL, clen = min(kVjpL, geo.len - k0);
     const bool has_next = k0 + clen < geo.len;
     const long base = blk * geo.inc * geo.len + off + (long)k0 * geo.inc, inc = geo.inc;
+    const long idx = c * geo.count + j;
     Chunk<kVjpL> ch;
     double g0[KEEP ? kVjpL : 1] = {};   // the cotangents as they came in (VJP_PD: zeta): the epilogue wants them next to the means
+    // (y: the chunk's samples, walked by chunk_load; or its code word, one coalesced load)
+    auto load = [&](auto cot) {
+        if constexpr (WORDS) vjp::chunk_load_steps(ch, clen, has_next, y[idx], cot);
+        else vjp::chunk_load(ch, clen, has_next, [&](int k) { return y[base + (long)k * inc]; }, cot);
+    };
     if constexpr (vjp_forms_cotangent(MODE)) {
-        vjp::chunk_load(ch, clen, has_next, [&](int k) { return y[base + (long)k * inc]; }, [&](int k) {
+        load([&](int k) {
             const long i = base + (long)k * inc;
             const double z = epi.zeta ? epi.zeta[i] : 0.0;
             if constexpr (MODE == VJP_PD) g0[k] = z;
             return vjp_pd_cotangent(epi, g, i, z);
         });
     } else {
-        vjp::chunk_load(ch, clen, has_next, [&](int k) { return y[base + (long)k * inc]; }, [&](int k) { return g[base + (long)k * inc]; });
+        load([&](int k) { return g[base + (long)k * inc]; });
     }
     if constexpr (MODE == VJP_DR_ROW || MODE == VJP_PD2) {
 #pragma unroll
@@ -142,7 +162,6 @@ __global__ __launch_bounds__(256) void vjp_strided_kernel(const double *y, const
             if (k < clen) g0[k] = ch.g[k];
     }
     vjp::chunk_prefix(ch);
-    const long idx = c * geo.count + j;
     if (!WRITE) {
         S[idx] = vjp::chunk_summary(ch);
         return;
@@ -163,11 +182,12 @@ __global__ __launch_bounds__(64) void vjp_resolve_strided_kernel(const Summary *
 }
 
 // ---- contiguous fibres: wave = 64 consecutive chunks (of one fibre or of several), staged through LDS -------------------------------
-// S and R are indexed fibre * nch + chunk
-template <int MODE>
-__global__ __launch_bounds__(64) void vjp_contig_kernel(const double *y, const double *g, double *gx, double *gw, int len, long count, int nch,
+// S and R are indexed fibre * nch + chunk, and so are the code words when y is those: they are not staged (a lane's word is one
+// coalesced load), the ty tile then only carries gw out
+template <int MODE, class SRC>
+__global__ __launch_bounds__(64) void vjp_contig_kernel(const SRC *y, const double *g, double *gx, double *gw, int len, long count, int nch,
                                                         Summary *S, const Resolved *R, VjpEpi epi) {
-    constexpr bool WRITE = vjp_writes(MODE);
+    constexpr bool WRITE = vjp_writes(MODE), WORDS = vjp_from_words<SRC>();
     __shared__ double ty[64 * kVjpRow], tg[64 * kVjpRow];
     const int lane = threadIdx.x;
     const long unit = (long)blockIdx.x * 64 + lane;
@@ -183,17 +203,23 @@ __global__ __launch_bounds__(64) void vjp_contig_kernel(const double *y, const d
         const int e = i * 64 + lane, src = e / kVjpL, k = e % kVjpL;
         const long b = __shfl(base, src);
         if (k < __shfl(clen, src)) {
-            ty[src * kVjpRow + k] = y[b + k];
+            if constexpr (!WORDS) ty[src * kVjpRow + k] = y[b + k];
             if constexpr (vjp_forms_cotangent(MODE)) tg[src * kVjpRow + k] = vjp_pd_cotangent(epi, g, b + k, epi.zeta ? epi.zeta[b + k] : 0.0);
             else tg[src * kVjpRow + k] = g[b + k];
         }
     }
-    if (has_next) ty[lane * kVjpRow + clen] = y[base + clen];
+    if constexpr (!WORDS)
+        if (has_next) ty[lane * kVjpRow + clen] = y[base + clen];
     __syncthreads();
     Chunk<kVjpL> ch;
     if (valid) {
-        const double *my = ty + lane * kVjpRow, *mg = tg + lane * kVjpRow;
-        vjp::chunk_load(ch, clen, has_next, [&](int k) { return my[k]; }, [&](int k) { return mg[k]; });
+        const double *mg = tg + lane * kVjpRow;
+        if constexpr (WORDS) {
+            vjp::chunk_load_steps(ch, clen, has_next, y[unit], [&](int k) { return mg[k]; });
+        } else {
+            const double *my = ty + lane * kVjpRow;
+            vjp::chunk_load(ch, clen, has_next, [&](int k) { return my[k]; }, [&](int k) { return mg[k]; });
+        }
         vjp::chunk_prefix(ch);
     }
     if (!WRITE) {
@@ -278,13 +304,72 @@ __global__ __launch_bounds__(256) void vjp_resolve_contig_kernel(const Summary *
     }
 }
 
+// ---- step codes: y -> one word per chunk (vjpcore.hpp: chunk_codes), in the geometries and the record order of the kernels above --------
+// Each reads y once plus every chunk's next sample and writes its own word: no atomics, the same words every time.
+__global__ __launch_bounds__(256) void vjp_encode_strided_kernel(const double *y, unsigned *W, FibreGeom geo, int nch) {
+    const long unit = (long)blockIdx.x * 4 + (threadIdx.x >> 6), groups = (geo.count + 63) / 64;
+    if (unit >= groups * nch) return;
+    long grp, c;
+    divmod_nonneg(unit, (long)nch, grp, c);
+    const long j = grp * 64 + (threadIdx.x & 63);
+    if (j >= geo.count) return;
+    long blk, off;
+    divmod_nonneg(j, geo.inc, blk, off);
+    const int k0 = (int)c * kVjpL, clen = min(kVjpL, geo.len - k0);
+    const bool has_next = k0 + clen < geo.len;
+    const long base = blk * geo.inc * geo.len + off + (long)k0 * geo.inc, inc = geo.inc;
+    W[c * geo.count + j] = vjp::chunk_codes<kVjpL>(clen, has_next, [&](int k) { return y[base + (long)k * inc]; });
+}
+
+__global__ __launch_bounds__(64) void vjp_encode_contig_kernel(const double *y, unsigned *W, int len, long count, int nch) {
+    __shared__ double ty[64 * kVjpRow];
+    const int lane = threadIdx.x;
+    const long unit = (long)blockIdx.x * 64 + lane;
+    const bool valid = unit < count * nch;
+    long j = 0, c = 0;
+    if (valid) divmod_nonneg(unit, (long)nch, j, c);
+    const int k0 = (int)c * kVjpL, clen = valid ? min(kVjpL, len - k0) : 0;
+    const bool has_next = valid && k0 + clen < len;
+    const long base = j * len + k0;
+#pragma unroll
+    for (int i = 0; i < kVjpL; i++) {
+        const int e = i * 64 + lane, src = e / kVjpL, k = e % kVjpL;
+        const long b = __shfl(base, src);
+        if (k < __shfl(clen, src)) ty[src * kVjpRow + k] = y[b + k];
+    }
+    if (has_next) ty[lane * kVjpRow + clen] = y[base + clen];
+    __syncthreads();
+    if (!valid) return;
+    const double *my = ty + lane * kVjpRow;
+    W[unit] = vjp::chunk_codes<kVjpL>(clen, has_next, [&](int k) { return my[k]; });
+}
+
+// the segment counts from the words alone: 1 + the steps of the fibre.  One lane per strided fibre, one wave per contiguous one.
+__global__ __launch_bounds__(64) void vjp_count_strided_kernel(const unsigned *W, int nch, long count, int *nseg) {
+    const long j = (long)blockIdx.x * 64 + threadIdx.x;
+    if (j >= count) return;
+    int steps = 0;
+    for (int c = 0; c < nch; c++) steps += __popc(W[c * count + j] & 0xffffu);
+    nseg[j] = steps + 1;
+}
+__global__ __launch_bounds__(256) void vjp_count_contig_kernel(const unsigned *W, int nch, long count, int *nseg) {
+    const int lane = threadIdx.x & 63;
+    const long j = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (j >= count) return;   // (the whole wave)
+    int steps = 0;
+    for (int c = lane; c < nch; c += 64) steps += __popc(W[j * nch + c] & 0xffffu);
+    for (int o = 32; o > 0; o >>= 1) steps += __shfl_xor(steps, o);
+    if (lane == 0) nseg[j] = steps + 1;
+}
+
 }  // namespace
 
 namespace {
 
 // phases A, B and C<MODE> of one sweep's derivative on the stream; S and R hold geo.count * ceil(geo.len / kVjpL) records.  gx == null: no phase C.
-template <int MODE>
-void vjp_launch(const double *y, const double *g, double *gx, double *gw, int *nseg, const FibreGeom &geo, Summary *S, Resolved *R,
+// y: the sweep's output, or (SRC = unsigned) its code words in the layout of S and R.
+template <int MODE, class SRC>
+void vjp_launch(const SRC *y, const double *g, double *gx, double *gw, int *nseg, const FibreGeom &geo, Summary *S, Resolved *R,
                 const VjpEpi &epi, hipStream_t s) {
     constexpr int A = MODE == VJP_PD ? VJP_PD_SUMMARY : VJP_SUMMARY;   // (phase A forms the cotangent the way phase C will)
     const VjpEpi epa = MODE == VJP_PD ? epi : VjpEpi{};
@@ -292,20 +377,41 @@ void vjp_launch(const double *y, const double *g, double *gx, double *gw, int *n
     const long units = geo.count * nch;
     if (geo.inc == 1) {
         const unsigned blocks = (unsigned)((units + 63) / 64), fibres4 = (unsigned)((geo.count + 3) / 4);
-        hipLaunchKernelGGL(vjp_contig_kernel<A>, dim3(blocks), dim3(64), 0, s, y, g, gx, gw, geo.len, geo.count, nch, S, R, epa);
+        hipLaunchKernelGGL((vjp_contig_kernel<A, SRC>), dim3(blocks), dim3(64), 0, s, y, g, gx, gw, geo.len, geo.count, nch, S, R, epa);
         hipLaunchKernelGGL(vjp_resolve_contig_kernel, dim3(fibres4), dim3(256), 0, s, S, R, nch, geo.count, nseg);
-        if (gx) hipLaunchKernelGGL(vjp_contig_kernel<MODE>, dim3(blocks), dim3(64), 0, s, y, g, gx, gw, geo.len, geo.count, nch, S, R, epi);
+        if (gx) hipLaunchKernelGGL((vjp_contig_kernel<MODE, SRC>), dim3(blocks), dim3(64), 0, s, y, g, gx, gw, geo.len, geo.count, nch, S, R, epi);
     } else {
         const long waves = ((geo.count + 63) / 64) * nch;
         const unsigned blocks = (unsigned)((waves + 3) / 4), fibres64 = (unsigned)((geo.count + 63) / 64);
-        hipLaunchKernelGGL(vjp_strided_kernel<A>, dim3(blocks), dim3(256), 0, s, y, g, gx, gw, geo, nch, S, R, epa);
+        hipLaunchKernelGGL((vjp_strided_kernel<A, SRC>), dim3(blocks), dim3(256), 0, s, y, g, gx, gw, geo, nch, S, R, epa);
         hipLaunchKernelGGL(vjp_resolve_strided_kernel, dim3(fibres64), dim3(64), 0, s, S, R, nch, geo.count, nseg);
-        if (gx) hipLaunchKernelGGL(vjp_strided_kernel<MODE>, dim3(blocks), dim3(256), 0, s, y, g, gx, gw, geo, nch, S, R, epi);
+        if (gx) hipLaunchKernelGGL((vjp_strided_kernel<MODE, SRC>), dim3(blocks), dim3(256), 0, s, y, g, gx, gw, geo, nch, S, R, epi);
     }
     PTV_HIP(hipGetLastError());
 }
 
 long vjp_units(const FibreGeom &geo) { return geo.count * ((geo.len + kVjpL - 1) / kVjpL); }
+
+// the same from whichever the tape kept: the code words when there are any, else the sweep's output
+template <int MODE>
+void vjp_launch_taped(const double *y, const unsigned *words, const double *g, double *gx, double *gw, const FibreGeom &geo, Summary *S, Resolved *R,
+                const VjpEpi &epi, hipStream_t s) {
+    if (words) vjp_launch<MODE>(words, g, gx, gw, nullptr, geo, S, R, epi, s);
+    else       vjp_launch<MODE>(y, g, gx, gw, nullptr, geo, S, R, epi, s);
+}
+
+// W[vjp_units(geo)] <- the step codes of y
+void vjp_encode(const double *y, unsigned *W, const FibreGeom &geo, hipStream_t s) {
+    const int nch = (geo.len + kVjpL - 1) / kVjpL;
+    if (geo.inc == 1) {
+        const unsigned blocks = (unsigned)((geo.count * nch + 63) / 64);
+        hipLaunchKernelGGL(vjp_encode_contig_kernel, dim3(blocks), dim3(64), 0, s, y, W, geo.len, geo.count, nch);
+    } else {
+        const long waves = ((geo.count + 63) / 64) * nch;
+        hipLaunchKernelGGL(vjp_encode_strided_kernel, dim3((unsigned)((waves + 3) / 4)), dim3(256), 0, s, y, W, geo, nch);
+    }
+    PTV_HIP(hipGetLastError());
+}
 
 }  // namespace
 
@@ -317,6 +423,38 @@ void tv1_fibres_vjp(const double *y, const double *g, double *gx, double *gw, in
     if (geo.len == 1) gw = nullptr;   // no edges
     if (!g) g = y;                    // (segment counts alone: phase A sums something, phase C does not run)
     vjp_launch<VJP_PLAIN>(y, g, gx, gw, nseg, geo, S.as<Summary>(), R.as<Resolved>(), VjpEpi{}, s);
+    PTV_HIP(hipStreamSynchronize(s));   // (the scratch goes back to the pool behind this)
+}
+
+long tv1_steps_words(const int *ns, int nds, int dim) {
+    const FibreGeom geo = fibres_along(ns, nds, dim);
+    return (geo.count <= 0 || geo.len <= 0) ? 0 : vjp_units(geo);
+}
+
+void tv1_fibres_steps(const double *y, unsigned *steps, const int *ns, int nds, int dim, hipStream_t s) {
+    const FibreGeom geo = fibres_along(ns, nds, dim);
+    if (geo.count <= 0 || geo.len <= 0) return;
+    vjp_encode(y, steps, geo, s);
+    PTV_HIP(hipStreamSynchronize(s));
+}
+
+void tv1_fibres_vjp_steps(const unsigned *steps, const double *g, double *gx, double *gw, int *nseg, const int *ns, int nds, int dim,
+                          hipStream_t s) {
+    const FibreGeom geo = fibres_along(ns, nds, dim);
+    if (geo.count <= 0 || geo.len <= 0) return;
+    const int nch = (geo.len + kVjpL - 1) / kVjpL;
+    if (!gx) {   // the segment counts alone: the words hold them
+        if (!nseg) return;
+        if (geo.inc == 1) hipLaunchKernelGGL(vjp_count_contig_kernel, dim3((unsigned)((geo.count + 3) / 4)), dim3(256), 0, s, steps, nch, geo.count, nseg);
+        else              hipLaunchKernelGGL(vjp_count_strided_kernel, dim3((unsigned)((geo.count + 63) / 64)), dim3(64), 0, s, steps, nch, geo.count, nseg);
+        PTV_HIP(hipGetLastError());
+        PTV_HIP(hipStreamSynchronize(s));
+        return;
+    }
+    const long units = vjp_units(geo);
+    Scratch S(sizeof(Summary) * (size_t)units), R(sizeof(Resolved) * (size_t)units);
+    if (geo.len == 1) gw = nullptr;   // no edges
+    vjp_launch<VJP_PLAIN>(steps, g, gx, gw, nseg, geo, S.as<Summary>(), R.as<Resolved>(), VjpEpi{}, s);
     PTV_HIP(hipStreamSynchronize(s));   // (the scratch goes back to the pool behind this)
 }
 
@@ -332,9 +470,13 @@ __global__ __launch_bounds__(256) void dr_vjp_mean_term_kernel(double *gU, long 
 
 }  // namespace
 
-size_t dr2_vjp_tape_bytes(size_t M, size_t N, size_t B, int maxit) {
+size_t dr2_vjp_tape_bytes(size_t M, size_t N, size_t B, int maxit, int tape) {
     if (maxit <= 0) maxit = MAX_ITERS_DR;
-    return 2 * ((size_t)maxit + 1) * sizeof(double) * M * N * B;
+    if (!tape) return 2 * ((size_t)maxit + 1) * sizeof(double) * M * N * B;
+    // step codes: a word array per sweep output, and the two arrays the sweeps write into
+    const int ns[3] = {(int)M, (int)N, (int)B};
+    const size_t words = (size_t)tv1_steps_words(ns, 3, 0) + (size_t)tv1_steps_words(ns, 3, 1);
+    return ((size_t)maxit + 1) * words * sizeof(unsigned) + 2 * sizeof(double) * M * N * B;
 }
 
 // Forward: the recurrence of dr2_norms (solvers.hip) on B stacked images with the sweep outputs x1_k, x2_k kept, k = 0 .. maxit (the last
@@ -345,8 +487,10 @@ size_t dr2_vjp_tape_bytes(size_t M, size_t N, size_t B, int maxit) {
 //   k = maxit-1 .. 0
 //          a = P_r gbar : gU += a, c = 2 a - gbar, gbar -= a, gW2 += gw   |  d = P_c c : gbar += d, gW1 += gw
 //   end    gU += 2 sum(gbar) / (M N) per image
+// tape = 1: x1_k and x2_k are written into two arrays that every iteration reuses and encoded behind their sweep (vjp_encode); the
+// reverse loop is the same with the words of sweep k where y was.
 void dr2_vjp(size_t M, size_t N, size_t B, const double *unary, double W1, double W2, const double *W1m, const double *W2m, const double *g,
-             double *out, double *gU, double *gW1, double *gW2, double *glam, int maxit, hipStream_t s) {
+             double *out, double *gU, double *gW1, double *gW2, double *glam, int maxit, int tape, hipStream_t s) {
     const long n1 = (long)(M * N), n = n1 * (long)B;
     if (maxit <= 0) maxit = MAX_ITERS_DR;
     if (n == 0) return;
@@ -355,10 +499,15 @@ void dr2_vjp(size_t M, size_t N, size_t B, const double *unary, double W1, doubl
     const long e1 = (long)((M - 1) * N), e2 = (long)(M * (N - 1));   // edges per image
     const size_t bytes = sizeof(double) * (size_t)n;
 
-    Scratch tape(dr2_vjp_tape_bytes(M, N, B, maxit)), t(bytes), v(bytes);
+    Scratch kept(dr2_vjp_tape_bytes(M, N, B, maxit, tape)), t(bytes), v(bytes);
     Scratch partials(sizeof(double) * kReduceBlocks * B), sums(sizeof(double) * 2 * B);
-    auto x1 = [&](int k) { return tape.d() + (size_t)(2 * k) * (size_t)n; };
-    auto x2 = [&](int k) { return tape.d() + (size_t)(2 * k + 1) * (size_t)n; };
+    // tape = 0: 2 (maxit + 1) outputs ; tape = 1: the two live outputs, then per k the words of x1_k and of x2_k
+    const size_t wc = (size_t)vjp_units(cols), wr = (size_t)vjp_units(rows);
+    unsigned *const words = tape ? reinterpret_cast<unsigned *>(kept.d() + 2 * (size_t)n) : nullptr;
+    auto x1 = [&](int k) { return kept.d() + (tape ? 0 : (size_t)(2 * k) * (size_t)n); };
+    auto x2 = [&](int k) { return kept.d() + (tape ? (size_t)n : (size_t)(2 * k + 1) * (size_t)n); };
+    auto c1 = [&](int k) { return tape ? words + (size_t)k * (wc + wr) : nullptr; };
+    auto c2 = [&](int k) { return tape ? words + (size_t)k * (wc + wr) + wc : nullptr; };
     {   // seed of the geometry policy, like dr2: the image's edge statistics (the first array a sweep sees here is the constant t0)
         const int both[2] = {0, 1};
         const double *const wts[2] = {W1m, W2m};
@@ -372,6 +521,10 @@ void dr2_vjp(size_t M, size_t N, size_t B, const double *unary, double W1, doubl
         lincomb(v.d(), unary, 1.0, t.d(), -1.0, x1(k), last ? 1.0 : 2.0, nullptr, 0, n, s);
         tv1_fibres(v.d(), x2(k), ns, 3, 1, W2, W2m, s);
         if (!last) lincomb(t.d(), t.d(), 1.0, x1(k), -1.0, x2(k), 1.0, nullptr, 0, n, s);
+        if (tape) {
+            vjp_encode(x1(k), c1(k), cols, s);
+            vjp_encode(x2(k), c2(k), rows, s);
+        }
     }
     if (out) PTV_HIP(hipMemcpyAsync(out, x2(maxit), bytes, hipMemcpyDeviceToDevice, s));
 
@@ -390,8 +543,8 @@ void dr2_vjp(size_t M, size_t N, size_t B, const double *unary, double W1, doubl
         row.c = c;
         row.final = k == maxit;
         row.add_gw = col.add_gw = k != maxit;
-        vjp_launch<VJP_DR_ROW>(x2(k), row.final ? g : gbar, gbar, w2, nullptr, rows, S.as<Summary>(), R.as<Resolved>(), row, s);
-        vjp_launch<VJP_DR_COL>(x1(k), c, gbar, w1, nullptr, cols, S.as<Summary>(), R.as<Resolved>(), col, s);
+        vjp_launch_taped<VJP_DR_ROW>(x2(k), c2(k), row.final ? g : gbar, gbar, w2, rows, S.as<Summary>(), R.as<Resolved>(), row, s);
+        vjp_launch_taped<VJP_DR_COL>(x1(k), c1(k), c, gbar, w1, cols, S.as<Summary>(), R.as<Resolved>(), col, s);
     }
     sum_to(gbar, n1, (long)B, partials.d(), sums.d(), s);
     {
@@ -427,9 +580,13 @@ long total(const int *ns, int nds) {
 
 }  // namespace
 
-size_t pd_vjp_tape_bytes(int which, const int *ns, int nds, int npen, int iters) {
-    const size_t sweeps = which == 0 ? (npen == 1 ? 1 : 2 * (size_t)iters) : (size_t)npen * (size_t)iters;
-    return sweeps * sizeof(double) * (size_t)total(ns, nds);
+size_t pd_vjp_tape_bytes(int which, const double *dims, const int *ns, int nds, int npen, int iters, int tape) {
+    const size_t K = (which == 0 && npen == 1) ? 1 : (size_t)iters;   // (one term: every iteration repeats the first)
+    if (!tape) return K * (size_t)npen * sizeof(double) * (size_t)total(ns, nds);
+    // step codes: a word array per sweep output, and one array per term for the sweeps to write into
+    size_t words = 0;
+    for (int i = 0; i < npen; i++) words += (size_t)tv1_steps_words(ns, nds, (int)(dims[i] - 1));
+    return K * words * sizeof(unsigned) + (size_t)npen * sizeof(double) * (size_t)total(ns, nds);
 }
 
 namespace {
@@ -465,26 +622,34 @@ void sum_terms(const std::vector<TermGw> &gw, double *glam, hipStream_t s) {
 // X and Pb are one array from the first reverse iteration on, so the state is X and the difference D = X - Qb, and in those
 //   a = P_1 D ; Zc = a - D  (last iteration: Zc = a) ; b = P_0 Zc ; X += b  (last: X = b) ; D = b - Zc
 // two launches of three phases, D rewritten in place by both, X = gy touched by the second alone.  One term: a single sweep.
+// tape = 1: z and x' are two arrays that every iteration reuses, encoded behind their sweep (x' is still read by the next iteration's
+// first two steps, which is before its sweep rewrites it).
 void pd2_vjp(const double *y, const double *lambdas, const double *dims, const int *ns, int nds, int npen, int K, const double *g, double *x,
-             double *gy, double *glam, hipStream_t s) {
+             double *gy, double *glam, int tape, hipStream_t s) {
     const long n = total(ns, nds);
     const size_t bytes = sizeof(double) * (size_t)n;
     const int d0 = (int)(dims[0] - 1), d1 = npen >= 2 ? (int)(dims[1] - 1) : d0;
     const FibreGeom g0 = fibres_along(ns, nds, d0), g1 = fibres_along(ns, nds, d1);
-    Scratch tape(pd_vjp_tape_bytes(0, ns, nds, npen, K));
+    Scratch kept(pd_vjp_tape_bytes(0, dims, ns, nds, npen, K, tape));
+    // tape = 1: the live outputs (one per term), then per k the words of z_k and of x'_k
+    const size_t w0 = (size_t)vjp_units(g0), w1 = npen >= 2 ? (size_t)vjp_units(g1) : 0;
+    unsigned *const words = tape ? reinterpret_cast<unsigned *>(kept.d() + (size_t)npen * (size_t)n) : nullptr;
     std::vector<TermGw> gw((size_t)npen);
     term_gw(gw[0], g0, glam != nullptr);
     if (npen >= 2) term_gw(gw[1], g1, glam != nullptr);
     const long units = std::max(vjp_units(g0), vjp_units(g1));
     Scratch S(sizeof(Summary) * (size_t)units), R(sizeof(Resolved) * (size_t)units);
     if (npen == 1) {   // (x + p stays y: every iteration repeats the first)
-        tv1_fibres(y, tape.d(), ns, nds, d0, lambdas[0], nullptr, s);
-        if (x) PTV_HIP(hipMemcpyAsync(x, tape.d(), bytes, hipMemcpyDeviceToDevice, s));
-        vjp_launch<VJP_PLAIN>(tape.d(), g, gy, gw[0].d(), nullptr, g0, S.as<Summary>(), R.as<Resolved>(), VjpEpi{}, s);
+        tv1_fibres(y, kept.d(), ns, nds, d0, lambdas[0], nullptr, s);
+        if (tape) vjp_encode(kept.d(), words, g0, s);
+        if (x) PTV_HIP(hipMemcpyAsync(x, kept.d(), bytes, hipMemcpyDeviceToDevice, s));
+        vjp_launch_taped<VJP_PLAIN>(kept.d(), words, g, gy, gw[0].d(), g0, S.as<Summary>(), R.as<Resolved>(), VjpEpi{}, s);
     } else {
         Scratch t(bytes), p(bytes), q(bytes);
-        auto zk = [&](int k) { return tape.d() + (size_t)(2 * k) * (size_t)n; };
-        auto xk = [&](int k) { return tape.d() + (size_t)(2 * k + 1) * (size_t)n; };
+        auto zk = [&](int k) { return kept.d() + (tape ? 0 : (size_t)(2 * k) * (size_t)n); };
+        auto xk = [&](int k) { return kept.d() + (tape ? (size_t)n : (size_t)(2 * k + 1) * (size_t)n); };
+        auto cz = [&](int k) { return tape ? words + (size_t)k * (w0 + w1) : nullptr; };
+        auto cx = [&](int k) { return tape ? words + (size_t)k * (w0 + w1) + w0 : nullptr; };
         const double *xc = y;
         for (int k = 0; k < K; k++) {
             if (k == 0) {   // p = q = 0
@@ -500,6 +665,10 @@ void pd2_vjp(const double *y, const double *lambdas, const double *dims, const i
                 tv1_fibres(t.d(), xk(k), ns, nds, d1, lambdas[1], nullptr, s);
                 lincomb(q.d(), q.d(), 1.0, zk(k), 1.0, xk(k), -1.0, nullptr, 0, n, s);
             }
+            if (tape) {
+                vjp_encode(zk(k), cz(k), g0, s);
+                vjp_encode(xk(k), cx(k), g1, s);
+            }
             xc = xk(k);
         }
         if (x) PTV_HIP(hipMemcpyAsync(x, xc, bytes, hipMemcpyDeviceToDevice, s));
@@ -509,8 +678,8 @@ void pd2_vjp(const double *y, const double *lambdas, const double *dims, const i
             second.final = first.final = k == K - 1;
             second.add_gw = first.add_gw = k != K - 1;
             first.gU = gy;
-            vjp_launch<VJP_PD2>(xk(k), second.final ? g : D, D, gw[1].d(), nullptr, g1, S.as<Summary>(), R.as<Resolved>(), second, s);
-            vjp_launch<VJP_PD2>(zk(k), D, D, gw[0].d(), nullptr, g0, S.as<Summary>(), R.as<Resolved>(), first, s);
+            vjp_launch_taped<VJP_PD2>(xk(k), cx(k), second.final ? g : D, D, gw[1].d(), g1, S.as<Summary>(), R.as<Resolved>(), second, s);
+            vjp_launch_taped<VJP_PD2>(zk(k), cz(k), D, D, gw[0].d(), g0, S.as<Summary>(), R.as<Resolved>(), first, s);
         }
     }
     if (glam) sum_terms(gw, glam, s);
@@ -523,12 +692,17 @@ void pd2_vjp(const double *y, const double *lambdas, const double *dims, const i
 //   for every i:  pi = chi / P - zeta_i ; a = P_i pi ; zeta_i += a ; chi' (+)= zeta_i             end: gy = chi'
 // one launch of three phases per term: pi is formed on load in phases A and C (chi is read by every term, so the sum for the next
 // iteration grows in a second array; the two change places), zeta_i is rewritten in place in the arrays the forward kept z_i in.
+// tape = 1: the p_i of an iteration live in P arrays that every iteration reuses (the combine needs all of them), each encoded behind
+// its sweep.
 void pdp_vjp(const double *y, const double *lambdas, const double *dims, const int *ns, int nds, int P, int K, const double *g, double *x,
-             double *gy, double *glam, hipStream_t s) {
+             double *gy, double *glam, int tape, hipStream_t s) {
     const long n = total(ns, nds);
     const size_t bytes = sizeof(double) * (size_t)n;
-    Scratch tape(pd_vjp_tape_bytes(1, ns, nds, P, K));
-    auto pk = [&](int k, int i) { return tape.d() + ((size_t)k * (size_t)P + (size_t)i) * (size_t)n; };
+    Scratch kept(pd_vjp_tape_bytes(1, dims, ns, nds, P, K, tape));
+    auto pk = [&](int k, int i) { return kept.d() + ((tape ? 0 : (size_t)k * (size_t)P) + (size_t)i) * (size_t)n; };
+    std::vector<size_t> woff((size_t)P + 1, 0);   // tape = 1: where term i's words start inside an iteration's block
+    unsigned *const words = tape ? reinterpret_cast<unsigned *>(kept.d() + (size_t)P * (size_t)n) : nullptr;
+    auto ck = [&](int k, int i) { return tape ? words + (size_t)k * woff[(size_t)P] + woff[(size_t)i] : nullptr; };
     std::vector<std::unique_ptr<Scratch>> z;
     std::vector<FibreGeom> geo;
     std::vector<TermGw> gw((size_t)P);
@@ -538,6 +712,7 @@ void pdp_vjp(const double *y, const double *lambdas, const double *dims, const i
         geo.push_back(fibres_along(ns, nds, (int)(dims[i] - 1)));
         term_gw(gw[(size_t)i], geo.back(), glam != nullptr);
         units = std::max(units, vjp_units(geo.back()));
+        woff[(size_t)i + 1] = woff[(size_t)i] + (size_t)vjp_units(geo.back());
         PTV_HIP(hipMemcpyAsync(z.back()->d(), y, bytes, hipMemcpyDeviceToDevice, s));
     }
     Scratch xa(bytes), xb(bytes), partials(sizeof(double) * kReduceBlocks), acc(sizeof(double));
@@ -558,6 +733,7 @@ void pdp_vjp(const double *y, const double *lambdas, const double *dims, const i
         PtrPack pp{}, zp{};
         for (int i = 0; i < P; i++) {
             tv1_fibres(z[(size_t)i]->d(), pk(k, i), ns, nds, (int)(dims[i] - 1), lambdas[i], nullptr, s);
+            if (tape) vjp_encode(pk(k, i), ck(k, i), geo[(size_t)i], s);
             if (i < kMaxTerms) {
                 pp.v[i] = pk(k, i);
                 zp.v[i] = z[(size_t)i]->d();
@@ -582,7 +758,7 @@ void pdp_vjp(const double *y, const double *lambdas, const double *dims, const i
             e.gU = next;
             e.final = i == 0;
             e.add_gw = k != K - 1;
-            vjp_launch<VJP_PD>(pk(k, i), chi, z[(size_t)i]->d(), gw[(size_t)i].d(), nullptr, geo[(size_t)i], S.as<Summary>(), R.as<Resolved>(), e, s);
+            vjp_launch_taped<VJP_PD>(pk(k, i), ck(k, i), chi, z[(size_t)i]->d(), gw[(size_t)i].d(), geo[(size_t)i], S.as<Summary>(), R.as<Resolved>(), e, s);
         }
         chi = next;
     }
@@ -594,10 +770,10 @@ void pdp_vjp(const double *y, const double *lambdas, const double *dims, const i
 }  // namespace
 
 void pd_vjp(int which, const double *y, const double *lambdas, const double *dims, const int *ns, int nds, int npen, int iters, const double *g,
-            double *x, double *gy, double *glam, hipStream_t s) {
+            double *x, double *gy, double *glam, int tape, hipStream_t s) {
     if (total(ns, nds) == 0) return;
-    if (which == 0) pd2_vjp(y, lambdas, dims, ns, nds, npen, iters, g, x, gy, glam, s);
-    else            pdp_vjp(y, lambdas, dims, ns, nds, npen, iters, g, x, gy, glam, s);
+    if (which == 0) pd2_vjp(y, lambdas, dims, ns, nds, npen, iters, g, x, gy, glam, tape, s);
+    else            pdp_vjp(y, lambdas, dims, ns, nds, npen, iters, g, x, gy, glam, tape, s);
 }
 
 }  // namespace ptv

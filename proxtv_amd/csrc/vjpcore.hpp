@@ -19,6 +19,8 @@
 //                                                        to every chunk the run touches -- so a segment has one value, bit for bit
 //   phase C  chunk_load + chunk_prefix + chunk_means      the chunk again, with those means for its head and tail
 // Sums run left to right inside a chunk and across chunks: nothing depends on timing, the result is the same bits every run.
+// chunk_load is the only reader of y, and keeps of it two masks; chunk_codes packs those into a word per chunk and chunk_load_steps
+// fills a chunk from the word, so that phases A and C can run without y (the tape of step codes).
 #pragma once
 
 #include "certify_rule.hpp"
@@ -85,6 +87,40 @@ PTV_VJP_HD void chunk_load(Chunk<L> &c, int len, bool has_next, Y y, G g) {
             }
         }
     }
+}
+
+// ---- step codes: all that chunk_load keeps of y ----------------------------------------------------------------------------------
+// One 32-bit word per chunk of at most 16 samples: bit k = the edge behind sample k is a step, bit 16 + k = that step goes up; the
+// bits of edges the chunk does not own (beyond a short last chunk, behind the fibre's last sample) are 0.  chunk_codes walks y the
+// way chunk_load does, so chunk_load_steps(chunk_codes(y), g) leaves the Chunk chunk_load(y, g) leaves, bit for bit.
+constexpr int kCodeEdges = 16;
+
+template <int L, class Y>
+PTV_VJP_HD unsigned chunk_codes(int len, bool has_next, Y y) {
+    static_assert(L >= 1 && L <= kCodeEdges, "a code word holds 16 edges");
+    unsigned word = 0;
+    double a = y(0);
+#pragma unroll
+    for (int k = 0; k < L; k++) {
+        if (k < len && (k < len - 1 || has_next)) {
+            const double b = y(k + 1);
+            if (is_step(a, b)) word |= (b > a ? 0x10001u : 1u) << k;
+            a = b;
+        }
+    }
+    return word;
+}
+
+template <int L, class G>
+PTV_VJP_HD void chunk_load_steps(Chunk<L> &c, int len, bool has_next, unsigned word, G g) {
+    static_assert(L <= kCodeEdges, "a code word holds 16 edges");
+    c.len = len;
+    c.has_next = has_next;
+    c.step = word & 0xffffu;
+    c.up = word >> kCodeEdges;
+#pragma unroll
+    for (int k = 0; k < L; k++)
+        if (k < len) c.g[k] = g(k);
 }
 
 // g[k] <- the sum of g over the samples of k's segment up to k, inside the chunk, left to right

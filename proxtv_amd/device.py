@@ -256,7 +256,71 @@ def tv1_fibres_vjp(y, g, dim, need_gw=False, need_nseg=False, out=None):
     return gx, gw, nseg
 
 
-def dr2_vjp(x, g, w_col, w_row=None, max_iters=0, weights_col=None, weights_row=None, need_gw=False, need_y=False):
+def tv1_fibres_steps(y, dim):
+    """The step codes of ``y = tv1_fibres(x, w, dim[, weights])``: a 1-D int32 tensor, one 32-bit word per chunk of 16 samples of a fibre
+    (bit k: the edge behind sample k of the chunk is a step; bit 16 + k: it steps up -- include/proxtv_amd.h).  They are all
+    tv1_fibres_vjp reads of `y`, in 1/32 of its bytes: ``tv1_fibres_vjp_steps(steps, g, y.shape, dim)`` returns the bits of
+    ``tv1_fibres_vjp(y, g, dim)``.  The order of the words is the library's own and holds for the same shape and `dim`."""
+    _check(y, "y")
+    if not 0 <= int(dim) < y.dim():
+        raise ValueError(f"dim {dim} out of range for a {y.dim()}-D array")
+    ns = np.array(y.shape, dtype=np.int32)
+    with torch.cuda.device(y.device):
+        lib = _lib.require_device()
+        steps = torch.empty(lib.proxtv_tv1_steps_words(ns.ctypes.data, y.dim(), int(dim)), device=y.device, dtype=torch.int32)
+        lib.proxtv_tv1_fibres_steps_dev(y.data_ptr(), steps.data_ptr() if steps.numel() else 0, ns.ctypes.data, y.dim(), int(dim),
+                                        _stream(y.device))
+    _lib.check("device.tv1_fibres_steps")
+    return steps
+
+
+def tv1_fibres_vjp_steps(steps, g, shape, dim, need_gw=False, need_nseg=False, out=None):
+    """``tv1_fibres_vjp(y, g, dim, ...)`` from ``steps = tv1_fibres_steps(y, dim)`` instead of `y` (`shape` is y's): the same
+    (gx, gw | None, nseg | None), bit for bit.  g = None: the segment counts alone, (None, None, nseg)."""
+    shape = tuple(int(v) for v in shape)
+    dim = int(dim)
+    if not 0 <= dim < len(shape):
+        raise ValueError(f"dim {dim} out of range for a {len(shape)}-D array")
+    if not (isinstance(steps, torch.Tensor) and steps.is_cuda and steps.dtype == torch.int32 and steps.is_contiguous()):
+        raise ValueError("steps: expected a contiguous int32 CUDA tensor (device.tv1_fibres_steps)")
+    ns = np.array(shape, dtype=np.int32)
+    lib = _lib.load()
+    if steps.numel() != lib.proxtv_tv1_steps_words(ns.ctypes.data, len(shape), dim):
+        raise ValueError(f"steps: {steps.numel()} words, an array of shape {shape} has "
+                         f"{lib.proxtv_tv1_steps_words(ns.ctypes.data, len(shape), dim)} along dimension {dim}")
+    gx = gw = nseg = None
+    if g is not None:
+        if not (isinstance(g, torch.Tensor) and g.is_cuda and g.dtype == torch.float64):
+            raise ValueError("g: expected a float64 CUDA tensor")
+        if g.device != steps.device:
+            raise ValueError(f"g: lives on {g.device}, the steps on {steps.device}")
+        if tuple(g.shape) != shape:
+            raise ValueError(f"g: shape {tuple(g.shape)}, expected {shape}")
+        if not _is_colmajor(g):
+            g = to_colmajor(g)
+        gx = _out(out, g)
+        if need_gw:
+            wshape = list(shape)
+            wshape[dim] -= 1
+            gw = colmajor_empty(wshape, device=g.device)
+    if need_nseg or g is None:
+        nseg = _counts_empty(shape, dim, steps.device)
+    ptr = lambda t: t.data_ptr() if t is not None and t.numel() else 0   # noqa: E731
+    with torch.cuda.device(steps.device):
+        lib = _lib.require_device()
+        lib.proxtv_tv1_fibres_vjp_steps_dev(ptr(steps), ptr(g), ptr(gx), ptr(gw), ptr(nseg), ns.ctypes.data, len(shape), dim,
+                                            _stream(steps.device))
+    _lib.check("device.tv1_fibres_vjp_steps")
+    return gx, gw, nseg
+
+
+def _tape(tape):
+    if tape not in ("outputs", "steps"):
+        raise ValueError(f"tape: 'outputs' or 'steps', got {tape!r}")
+    return 1 if tape == "steps" else 0
+
+
+def dr2_vjp(x, g, w_col, w_row=None, max_iters=0, weights_col=None, weights_row=None, need_gw=False, need_y=False, tape="outputs"):
     """The derivative of the Douglas-Rachford solves ``tv1_2d(x, w_col, w_row=w_row)`` / ``tv1w_2d(x, weights_col, weights_row)`` /
     ``tv1_2d_batch`` applied to the cotangent `g` of their result: returns (gx, gw_col, gw_row, glam, y).
 
@@ -264,9 +328,11 @@ def dr2_vjp(x, g, w_col, w_row=None, max_iters=0, weights_col=None, weights_row=
     the gradients in the per-edge penalties (the shapes of `weights_col` / `weights_row`, also for a uniform penalty) and glam, a numpy
     array of shape (2,) or (B, 2), their sums per image: the gradients in a uniform (w_col, w_row).  ``need_gw="sums"`` returns glam
     alone.  y (`need_y`) is the forward result of the call's own, unfused recurrence: device.tv1_2d's up to rounding.  One call:
-    proxtv_DR2_TV_vjp_dev (include/proxtv_amd.h), which keeps 2 (max_iters + 1) arrays of x's size in pool scratch while it runs.  A `g`
-    in another layout is copied."""
+    proxtv_DR2_TV_vjp_tape_dev (include/proxtv_amd.h), which keeps 2 (max_iters + 1) arrays of x's size in pool scratch while it runs
+    -- or, with ``tape="steps"``, the step codes of those arrays (1/32 of the bytes) and two arrays of x's size; every result is the same
+    bits.  A `g` in another layout is copied."""
     _check(x, "x")
+    tape = _tape(tape)
     if x.dim() not in (2, 3):
         raise ValueError(f"x: expected an (M, N) image or an (M, N, B) batch, got {x.dim()} dimensions")
     if not (isinstance(g, torch.Tensor) and g.is_cuda and g.dtype == torch.float64):
@@ -300,16 +366,16 @@ def dr2_vjp(x, g, w_col, w_row=None, max_iters=0, weights_col=None, weights_row=
     wptr = lambda t: 0 if t is None else (ptr(t) or x.data_ptr())        # noqa: E731
     with torch.cuda.device(x.device):
         lib = _lib.require_device()
-        lib.proxtv_DR2_TV_vjp_dev(M, N, B, ptr(x), float(w_col), float(w_row), wptr(weights_col), wptr(weights_row), ptr(g),
-                                  ptr(y), ptr(gx), ptr(gw_col), ptr(gw_row), glam.ctypes.data if need_gw else 0, int(max_iters),
-                                  _stream(x.device))
+        lib.proxtv_DR2_TV_vjp_tape_dev(M, N, B, ptr(x), float(w_col), float(w_row), wptr(weights_col), wptr(weights_row), ptr(g),
+                                       ptr(y), ptr(gx), ptr(gw_col), ptr(gw_row), glam.ctypes.data if need_gw else 0, int(max_iters),
+                                       tape, _stream(x.device))
     _lib.check("device.dr2_vjp")
     if glam is not None and x.dim() == 2:
         glam = glam[0]
     return gx, gw_col, gw_row, glam, y
 
 
-def tvgen_vjp(x, g, ws, ds, iters, method=None, need_glam=False, need_y=False):
+def tvgen_vjp(x, g, ws, ds, iters, method=None, need_glam=False, need_y=False, tape="outputs"):
     """The derivative of ``tvgen(x, ws, ds, method=method)`` applied to the cotangent `g` of its result: returns (gx, glam, y).
 
     `iters` is the iteration count the forward solve reported (``info[0]``): the call runs exactly that many iterations of its own,
@@ -317,9 +383,11 @@ def tvgen_vjp(x, g, ws, ds, iters, method=None, need_glam=False, need_y=False):
     method follows tvgen's dispatch (None: 'pd2' for two terms, otherwise 'pd'); 'pdr' and 'yang' have no derivative.  gx is the gradient
     in x.  glam (`need_glam`) is a numpy array with the gradient in every entry of `ws` as the user passes them (for 'pd' the library
     works with ws * len(ws); the chain rule through that scaling is applied here).  y (`need_y`) is the forward result of the call's own
-    recurrence: tvgen's up to rounding.  One call: proxtv_PD_TV_vjp_dev (include/proxtv_amd.h), which keeps len(ws) * iters ('pd') or
-    2 * iters ('pd2') arrays of x's size in pool scratch while it runs.  A `g` in another layout is copied."""
+    recurrence: tvgen's up to rounding.  One call: proxtv_PD_TV_vjp_tape_dev (include/proxtv_amd.h), which keeps len(ws) * iters ('pd') or
+    2 * iters ('pd2') arrays of x's size in pool scratch while it runs -- or, with ``tape="steps"``, their step codes (1/32 of the bytes)
+    and one array of x's size per term; every result is the same bits.  A `g` in another layout is copied."""
     _check(x, "x")
+    tape = _tape(tape)
     if not (isinstance(g, torch.Tensor) and g.is_cuda and g.dtype == torch.float64):
         raise ValueError("g: expected a float64 CUDA tensor")
     if g.device != x.device:
@@ -346,8 +414,9 @@ def tvgen_vjp(x, g, ws, ds, iters, method=None, need_glam=False, need_y=False):
     ptr = lambda t: t.data_ptr() if t is not None and t.numel() else 0   # noqa: E731
     with torch.cuda.device(x.device):
         lib = _lib.require_device()
-        lib.proxtv_PD_TV_vjp_dev(0 if method == "pd2" else 1, ptr(x), scaled.ctypes.data, dims.ctypes.data, ns.ctypes.data, x.dim(), npen,
-                                 int(iters), ptr(g), ptr(y), ptr(gx), glam.ctypes.data if need_glam else 0, _stream(x.device))
+        lib.proxtv_PD_TV_vjp_tape_dev(0 if method == "pd2" else 1, ptr(x), scaled.ctypes.data, dims.ctypes.data, ns.ctypes.data, x.dim(),
+                                      npen, int(iters), ptr(g), ptr(y), ptr(gx), glam.ctypes.data if need_glam else 0, tape,
+                                      _stream(x.device))
     _lib.check("device.tvgen_vjp")
     if glam is not None:
         glam *= scale
