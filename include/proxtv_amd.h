@@ -292,7 +292,8 @@ int proxtv_DR2_TV_vjp_dev(size_t M, size_t N, size_t B, const double *unary, dou
    inside those kernels.  What comes out is the derivative of the `iters`-step recurrence.  Limits: the dependence of the iteration count
    on the data through the stopping rule is NOT differentiated; the step rule and its two limits (kinks; the absolute 4e-10) are
    proxtv_tv1_fibres_vjp_dev's; the forward agrees with the fused solve to rounding, not bit for bit.  Per-edge weight maps and TV-L2 terms
-   are not covered (there is no `norms` argument).  A total size of 0: returns 1, nothing is written.  iters < 1, which = 0 with npen > 2,
+   are not covered (there is no `norms` argument; the TV-L2 fibre prox alone is differentiated by proxtv_tv2_fibres_vjp_dev, from which
+   such a loop can be composed).  A total size of 0: returns 1, nothing is written.  iters < 1, which = 0 with npen > 2,
    a dimension out of range, a missing y / g / gy, any overlap except gy == g, or a tape beyond the cap: returns 0 with proxtv_last_error
    set and nothing written.  No atomics: the same call gives the same bits.  Synchronises the stream; returns 1 on success. */
 int proxtv_PD_TV_vjp_dev(int which /*0: PD2_TV, 1: PD_TV*/, const double *y, const double *lambdas /*host, as the forward takes them*/,
@@ -353,6 +354,39 @@ int proxtv_tvp_fibres_dev(const double *in, double *out, const int *ns, int nds,
                           void *stream);
 int proxtv_DR2_TVp_dev(size_t M, size_t N, const double *unary, double W1, double W2, double norm1, double norm2,
                        double *s, int maxit, double *info, void *stream);
+
+/* The TV-L2 fibre prox on its own, with its multiplier: out = argmin 1/2 ||x - in||^2 + lambda ||Dx||_2 along `dim` of every fibre --
+   the bits of proxtv_tvp_fibres_dev(p = 2).  Per fibre of n samples, D the (n-1) x n difference matrix and T = D D' = tridiag(-1, 2, -1):
+   out = in - D'u, where either u = T^-1 D in lies inside the ball ||u|| <= lambda (out is then the mean of in), or (T + mu I) u = D in
+   with ||u|| = lambda and mu > 0 (then D out = mu u, so mu = ||D out|| / lambda).
+     mu          DEVICE double per fibre, or NULL: that multiplier, in the column-major order of the array with `dim` removed (as nseg is
+                 laid out for TV-L1).  Exactly 0.0 where u lies inside the ball, for ns[dim] == 1 and for lambda <= 0.  The case cannot be
+                 read off `out` in floating point (inside the ball D out is ~1e-17, not 0), which is why it is an output.  0.0 can also
+                 mean "active by less than one Newton step": where ||T^-1 D in|| exceeds lambda by a rounding margin and the first
+                 Newton step does not raise mu, the iteration stops at mu = 0 and `out` is the mean up to that margin -- the kink.
+   out may overlap in (the solve then goes through scratch); mu may overlap neither.  A total size of 0: returns 1, nothing is written.
+   Synchronises the stream; returns 1, or 0 with proxtv_last_error set. */
+int proxtv_tv2_fibres_dev(const double *in, double *out, double *mu /*or NULL*/, const int *ns /*host*/, int nds, int dim, double lambda,
+                          void *stream);
+
+/* The derivative of that prox: y and mu are what proxtv_tv2_fibres_dev returned for the same ns / dim / lambda.  With M = T + mu I
+   (symmetric positive definite), a cotangent g and h = D g, per fibre:
+     mu > 0      p = M^-1 h,  q = M^-1 (D y),  kappa = (h'q) / ((D y)'q)
+                 gx = g - D'(p - kappa q)                                   (shape of y; gx may be g itself)
+                 glam = -mu lambda kappa                                    (glam or NULL: DEVICE double per fibre, laid out as mu; for one
+                                                                             lambda shared by all fibres d/dlambda is the sum of glam)
+     mu == 0     gx = mean(g) on every sample, glam = 0
+     ns[dim] == 1 or lambda <= 0:  gx = g, glam = 0
+   The Jacobian is symmetric, so this one call is the VJP and the JVP in x.  At the kink ||T^-1 D x|| = lambda the prox is not
+   differentiable: mu records the branch the forward took and that branch's derivative is what comes out.  Two passes per fibre -- one
+   forward elimination on both right-hand sides, which also yields both dot products of kappa, one backward substitution on the combined
+   vector -- against the forward's 3-9 Newton iterations of two solves each; a few long contiguous fibres (>= 16384 samples, the forward's
+   own condition) are solved parallel inside the fibre.  Scratch comes from the pool.  A total size of 0: returns 1, nothing is written.
+   A missing y / mu / g / gx, a dimension out of range, or any overlap except gx == g: returns 0 with proxtv_last_error set and nothing
+   written.  No atomics: the same call gives the same bits.  Synchronises the stream; returns 1 on success. */
+int proxtv_tv2_fibres_vjp_dev(const double *y, const double *mu, const double *g, double *gx /*may be g*/,
+                              double *glam /*device, one per fibre, or NULL*/, const int *ns /*host*/, int nds, int dim, double lambda,
+                              void *stream);
 int proxtv_PD_TVp_dev(int which, const double *y, const double *lambdas_scaled, const double *norms, const double *dims,
                       double *x, double *info, const int *ns, int nds, int npen, int maxIters, void *stream);
 

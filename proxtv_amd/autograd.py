@@ -12,7 +12,9 @@ solves are differentiated as loops, natively: forward is the fused device.tv1_2d
 saved, and backward is ONE device.dr2_vjp call, which replays the recurrence on the device and sweeps it in reverse.  The
 N-D entry tvgen is differentiated the same way through its two Dykstra loops ('pd2' / 'pd'): forward is the fused device.tvgen, backward
 ONE device.tvgen_vjp call with the iteration count the forward reported.  The other solvers (PDR, Yang, ...) are not
-differentiated: compose them from tv1_fibres and torch's pointwise operations.
+differentiated: compose them from tv1_fibres and torch's pointwise operations.  The TV-L2 fibre prox has its own derivative:
+tv2_fibres(x, w, dim) is device.tv2_fibres with ONE device.tv2_fibres_vjp call as backward; TV-L2 terms inside the solver
+derivatives are not covered -- compose such loops from tv1_fibres and tv2_fibres.
 
     y = autograd.tvgen(x, [w0, w1, w2], [1, 2, 3])   # a volume; every w a float or a 0-d float64 tensor
 
@@ -65,6 +67,37 @@ def tv1_fibres(x, w, dim, weights=None, tape="outputs"):
     if not wants:
         return device.tv1_fibres(x, float(w), dim, weights)
     return _TV1Fibres.apply(x, w, weights, int(dim), tape)
+
+
+class _TV2Fibres(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, w, dim):
+        y, mu = device.tv2_fibres(_colmajor(x.detach()), float(w), dim, return_mu=True)
+        ctx.save_for_backward(y, mu)
+        ctx.dim, ctx.w = dim, float(w)
+        ctx.w_device = w.device if isinstance(w, torch.Tensor) else None
+        return y
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, gy):
+        y, mu = ctx.saved_tensors
+        need_x, need_w = ctx.needs_input_grad[:2]
+        res = device.tv2_fibres_vjp(y, mu, gy, ctx.w, ctx.dim, need_glam=need_w)
+        gx, glam = res if need_w else (res, None)
+        return (gx if need_x else None), (glam.sum().to(ctx.w_device) if need_w else None), None
+
+
+def tv2_fibres(x, w, dim):
+    """``device.tv2_fibres(x, w, dim)`` (the TV-L2 fibre prox, penalty ``w * ||diff||_2`` per fibre) with a graph behind it:
+    differentiable in x, and in w when w is a 0-d float64 tensor (its gradient comes back on that tensor's device).  The forward is
+    bit for bit device.tv2_fibres's and saves its output and the fibres' multipliers; backward is ONE device.tv2_fibres_vjp call plus,
+    for w, a sum (at the kink the branch the forward took is differentiated).  When nothing asks for a gradient this IS
+    device.tv2_fibres."""
+    _scalar_penalty(w, "w")
+    if not _wants(x, w):
+        return device.tv2_fibres(x, float(w), dim)
+    return _TV2Fibres.apply(x, w, int(dim))
 
 
 class _DR2(torch.autograd.Function):

@@ -12,6 +12,7 @@
 #include "solvers.hpp"
 #include "pointwise.hpp"
 #include "sweep.hpp"
+#include "tv2.hpp"
 
 using namespace ptv;
 
@@ -840,6 +841,55 @@ int proxtv_tvp_fibres_dev(const double *in, double *out, const int *ns, int nds,
         guard.commit(st);
         PTV_HIP(hipStreamSynchronize(st));
         scope.finish();
+    });
+}
+
+// whether [a, a + na) and [b, b + nb) (counted in doubles) share a byte
+static bool spans_overlap(const double *a, size_t na, const double *b, size_t nb) { return a && b && na && nb && a < b + nb && b < a + na; }
+
+int proxtv_tv2_fibres_dev(const double *in, double *out, double *mu, const int *ns, int nds, int dim, double lambda, void *stream) {
+    return guarded("proxtv_tv2_fibres_dev", nullptr, 1, [&] {
+        if (dim < 0 || dim >= nds) reject("dimension out of range");
+        const size_t n = (size_t)total(ns, nds);
+        if (n == 0) return;
+        if (!in || !out) reject("in and out are required");
+        const size_t nf = n / (size_t)ns[dim];
+        if (spans_overlap(mu, nf, in, n) || spans_overlap(mu, nf, out, n)) reject("mu overlaps in or out");
+        hipStream_t st = pick(stream);
+        SolveScope scope(st);
+        OutGuard guard(out, n, {{in, n}});
+        tv2_fibres(in, guard.ptr(), ns, nds, dim, lambda, st, mu);
+        guard.commit(st);
+        PTV_HIP(hipStreamSynchronize(st));
+        scope.finish();
+    });
+}
+
+int proxtv_tv2_fibres_vjp_dev(const double *y, const double *mu, const double *g, double *gx, double *glam, const int *ns, int nds, int dim,
+                              double lambda, void *stream) {
+    return guarded("proxtv_tv2_fibres_vjp_dev", nullptr, 1, [&] {
+        if (dim < 0 || dim >= nds) reject("dimension out of range");
+        const size_t n = (size_t)total(ns, nds);
+        if (n == 0) return;
+        if (!y || !mu || !g || !gx) reject("y, mu, g and gx are required");
+        // every array is read while others are written: none may overlap another, except that gx may BE g (tv2vjpcore.hpp)
+        const size_t nf = n / (size_t)ns[dim];
+        struct Span { const double *p; size_t n; bool out; const char *name; };
+        const Span spans[] = {{y, n, false, "y"}, {mu, nf, false, "mu"}, {g, n, false, "g"}, {gx, n, true, "gx"}, {glam, nf, true, "glam"}};
+        for (const Span &o : spans) {
+            if (!o.out || !o.p) continue;
+            for (const Span &i : spans) {
+                if (&i == &o || (&o == &spans[3] && &i == &spans[2] && gx == g)) continue;
+                if (i.out && &i > &o) continue;   // (a pair of outputs: once)
+                if (spans_overlap(i.p, i.n, o.p, o.n)) {
+                    set_error("%s overlaps %s (only gx may alias g, and then exactly)", o.name, i.name);
+                    throw HipFailure{hipErrorInvalidValue};
+                }
+            }
+        }
+        hipStream_t st = pick(stream);
+        tv2_fibres_vjp(y, mu, g, gx, glam, ns, nds, dim, lambda, st);
+        PTV_HIP(hipStreamSynchronize(st));
     });
 }
 

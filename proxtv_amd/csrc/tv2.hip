@@ -22,6 +22,8 @@
 // z, dual u).  Not a hot path of the headline; exact, batched, device-resident.
 #include "tv2.hpp"
 
+#include <vector>
+
 #include "pointwise.hpp"
 
 namespace ptv {
@@ -35,6 +37,7 @@ struct Tv2Args {
     double *x;
     double *d, *z, *u;   // scratch, laid out like the data
     double lam;
+    double *mu;          // or null: the multiplier of every fibre (0 exactly: u lies inside the ball, n == 1, lam <= 0)
 };
 
 // (tridiag(-1, a, -1)) out = rhs over one fibre.  REFACTOR: compute and store the pivots d (else reuse them).
@@ -118,6 +121,7 @@ __global__ __launch_bounds__(64) void tv2_fibres_kernel(Tv2Args p, FibreGeom g) 
     const int n = g.len, nn = n - 1;
     if (nn == 0 || !(p.lam > 0.0)) {
         for (int i = 0; i < n; i++) p.x[base + (long)i * inc] = p.y[base + (long)i * inc];
+        if (p.mu) p.mu[j] = 0.0;
         return;
     }
     double mu = 0.0;
@@ -134,6 +138,7 @@ __global__ __launch_bounds__(64) void tv2_fibres_kernel(Tv2Args p, FibreGeom g) 
             if (fabs(nu - p.lam) <= 1e-14 * p.lam) break;
         }
     }
+    if (p.mu) p.mu[j] = mu;
     // x = y + D'u
     double uprev = 0.0;
     for (int i0 = 0; i0 < n; i0 += kBlock) {
@@ -175,6 +180,10 @@ struct LongArgs {
     double *partial;    // [blocks]: dot-product partials
     int nn;
     double theta, etheta;   // a = 2 cosh(theta) ; exp(-theta)
+    // the derivative's passes (4, 5) only
+    const double *zh = nullptr;   // the eliminated D g (a PASS 0 run with y = g)
+    double *partial2 = nullptr;   // [blocks]: partials of the second dot product
+    const double *kap = nullptr;  // kappa, on the device
 };
 
 // g(k) = sinh(k theta) / sinh((k + 1) theta) = 1 / d_{k-1}  (g(0) = 0)
@@ -187,17 +196,31 @@ __device__ __forceinline__ double long_g(const LongArgs &p, long k) {
 }
 
 // PASS 0: forward, rhs = Dy -> z ; 1: forward, rhs = u -> z ; 2: backward -> u, partial = sum o^2 ; 3: backward, partial = sum u o
+// and for the derivative  4: PASS 0 with partial = sum z_i^2 / d_i, partial2 = sum zh_i z_i / d_i ;
+// 5: backward on zh - kappa z -> u, no sums
 // logical index k runs the way the recurrence does: forward i = k, backward i = nn - 1 - k.
 template <int PASS>
 __device__ __forceinline__ void long_coeffs(const LongArgs &p, long k, double &c, double &r) {
-    if (PASS <= 1) {
+    if (PASS <= 1 || PASS == 4) {
         c = long_g(p, k);
-        r = PASS == 0 ? p.y[k + 1] - p.y[k] : p.u[k];
+        r = PASS == 1 ? p.u[k] : p.y[k + 1] - p.y[k];
     } else {
         const long i = (long)p.nn - 1 - k;
         c = long_g(p, i + 1);
-        r = p.z[i] * c;
+        r = (PASS == 5 ? p.zh[i] - *p.kap * p.z[i] : p.z[i]) * c;
     }
+}
+
+// sum of `acc` over the block in a fixed order; the result is valid in thread 0
+__device__ __forceinline__ double long_block_sum(double acc, double *sc) {
+    __syncthreads();
+    sc[threadIdx.x] = acc;
+    __syncthreads();
+    for (int d = kLongThreads / 2; d > 0; d >>= 1) {
+        if ((int)threadIdx.x < d) sc[threadIdx.x] += sc[threadIdx.x + d];
+        __syncthreads();
+    }
+    return sc[0];
 }
 
 // ordered composition of the maps held by the threads of a block: after the call thread 0 holds the block's map; with SCAN every
@@ -292,33 +315,38 @@ __global__ __launch_bounds__(kLongThreads) void tv2_long_apply_kernel(LongArgs p
     double pc, pr;
     long_block_compose<true>(c, r, pc, pr, sc);
     double v = pr + pc * p.amap[2 * blockIdx.x];   // entering this thread's first element
-    double acc = 0.0;
+    double acc = 0.0, acc2 = 0.0;
 #pragma unroll
     for (int j = 0; j < kLongItems; j++) {
         if (k0 + j < p.nn) {
             v = rs[j] + cs[j] * v;
-            if (PASS <= 1) {
+            if (PASS <= 1 || PASS == 4) {
                 p.z[k0 + j] = v;
+                if (PASS == 4) {
+                    const double rd = long_g(p, k0 + j + 1);   // 1 / d_i
+                    acc += (v * v) * rd;
+                    acc2 += (p.zh[k0 + j] * v) * rd;
+                }
             } else {
                 const long i = (long)p.nn - 1 - (k0 + j);
                 if (PASS == 2) {
                     p.u[i] = v;
                     acc += v * v;
-                } else {
+                } else if (PASS == 3) {
                     acc += p.u[i] * v;
+                } else {
+                    p.u[i] = v;
                 }
             }
         }
     }
-    if (PASS >= 2) {   // block sum in a fixed order
-        __syncthreads();
-        sc[0][threadIdx.x] = acc;
-        __syncthreads();
-        for (int d = kLongThreads / 2; d > 0; d >>= 1) {
-            if ((int)threadIdx.x < d) sc[0][threadIdx.x] += sc[0][threadIdx.x + d];
-            __syncthreads();
-        }
-        if (threadIdx.x == 0) p.partial[blockIdx.x] = sc[0][0];
+    if (PASS >= 2 && PASS <= 4) {   // block sum in a fixed order
+        const double sum = long_block_sum(acc, sc[0]);
+        if (threadIdx.x == 0) p.partial[blockIdx.x] = sum;
+    }
+    if (PASS == 4) {
+        const double sum = long_block_sum(acc2, sc[0]);
+        if (threadIdx.x == 0) p.partial2[blockIdx.x] = sum;
     }
 }
 
@@ -343,10 +371,14 @@ __global__ __launch_bounds__(kLongThreads) void tv2_long_primal_kernel(const dou
     }
 }
 
-// sum of the result of one solve: returns sum o^2 (rhs = Dy; u <- o) or sum u o (rhs = u)
-double tv2_long_solve(LongArgs &p, bool rhs_diff, double mu, int blocks, double *dsum, hipStream_t s) {
+void long_set_mu(LongArgs &p, double mu) {
     p.theta = mu > 0.0 ? log1p(0.5 * mu + sqrt(mu + 0.25 * mu * mu)) : 0.0;   // acosh(1 + mu / 2)
     p.etheta = exp(-p.theta);
+}
+
+// sum of the result of one solve: returns sum o^2 (rhs = Dy; u <- o) or sum u o (rhs = u)
+double tv2_long_solve(LongArgs &p, bool rhs_diff, double mu, int blocks, double *dsum, hipStream_t s) {
+    long_set_mu(p, mu);
     const dim3 grid((unsigned)blocks), block(kLongThreads);
     if (rhs_diff) {
         hipLaunchKernelGGL(tv2_long_reduce_kernel<0>, grid, block, 0, s, p);
@@ -371,8 +403,8 @@ double tv2_long_solve(LongArgs &p, bool rhs_diff, double mu, int blocks, double 
     return h;
 }
 
-// one contiguous fibre of n samples; same iteration and stopping rule as tv2_fibres_kernel
-void tv2_long_fibre(const double *y, double *x, int n, double lam, hipStream_t s) {
+// one contiguous fibre of n samples; same iteration and stopping rule as tv2_fibres_kernel.  Returns the fibre's multiplier.
+double tv2_long_fibre(const double *y, double *x, int n, double lam, hipStream_t s) {
     const int nn = n - 1;
     const int blocks = (nn + kLongBlock - 1) / kLongBlock;
     Scratch z(sizeof(double) * (size_t)nn), u(sizeof(double) * (size_t)nn), amap(sizeof(double) * 2 * (size_t)blocks),
@@ -396,24 +428,123 @@ void tv2_long_fibre(const double *y, double *x, int n, double lam, hipStream_t s
     const int pb = (n + kLongThreads - 1) / kLongThreads;
     hipLaunchKernelGGL(tv2_long_primal_kernel, dim3((unsigned)(pb < 4096 ? pb : 4096)), dim3(kLongThreads), 0, s, y, u.d(), x, n, 1);
     PTV_HIP(hipGetLastError());
+    return mu;
+}
+
+// ---- the derivative of one LONG fibre: the same scans, no iteration -------------------------------------------------
+// per-block sums of g, left to right inside a thread, then the block's fixed tree
+__global__ __launch_bounds__(kLongThreads) void tv2_long_gsum_kernel(const double *g, int n, double *partial) {
+    __shared__ double sc[kLongThreads];
+    const long k0 = (long)blockIdx.x * kLongBlock + (long)threadIdx.x * kLongItems;
+    double a = 0.0;
+#pragma unroll
+    for (int j = 0; j < kLongItems; j++)
+        if (k0 + j < n) a += g[k0 + j];
+    const double sum = long_block_sum(a, sc);
+    if (threadIdx.x == 0) partial[blockIdx.x] = sum;
+}
+
+// gx = sum / n on every sample (the inside case), glam = 0
+__global__ __launch_bounds__(kLongThreads) void tv2_long_mean_kernel(const double *sum, int n, double *gx, double *glam) {
+    const double m = *sum / (double)n;
+    for (long i = (long)blockIdx.x * kLongThreads + threadIdx.x; i < n; i += (long)gridDim.x * kLongThreads) gx[i] = m;
+    if (glam && blockIdx.x == 0 && threadIdx.x == 0) *glam = 0.0;
+}
+
+// kappa = (sum partial2) / (sum partial), glam = -mu lam kappa; one workgroup, fixed order
+__global__ __launch_bounds__(kLongThreads) void tv2_long_kappa_kernel(const double *partial, const double *partial2, int blocks, double mu,
+                                                                       double lam, double *kap, double *glam) {
+    __shared__ double sc[kLongThreads];
+    double a = 0.0, a2 = 0.0;
+    for (int b = threadIdx.x; b < blocks; b += kLongThreads) {
+        a += partial[b];
+        a2 += partial2[b];
+    }
+    const double qq = long_block_sum(a, sc);
+    const double hq = long_block_sum(a2, sc);
+    if (threadIdx.x == 0) {
+        const double kappa = hq / qq;
+        *kap = kappa;
+        if (glam) *glam = -(mu * lam) * kappa;
+    }
+}
+
+void tv2_long_fibre_vjp(const double *y, double mu, const double *g, double *gx, double *glam, int n, double lam, hipStream_t s) {
+    const int nn = n - 1;
+    const int blocks = (nn + kLongBlock - 1) / kLongBlock;
+    const dim3 grid((unsigned)blocks), block(kLongThreads);
+    const int pb = (n + kLongThreads - 1) / kLongThreads;
+    const dim3 pgrid((unsigned)(pb < 4096 ? pb : 4096));
+    if (!(mu > 0.0)) {   // inside: the mean of g on every sample
+        const int gb = (n + kLongBlock - 1) / kLongBlock;
+        Scratch partial(sizeof(double) * (size_t)gb), dsum(sizeof(double));
+        hipLaunchKernelGGL(tv2_long_gsum_kernel, dim3((unsigned)gb), block, 0, s, g, n, partial.d());
+        hipLaunchKernelGGL(tv2_long_sum_kernel, dim3(1), block, 0, s, partial.d(), gb, dsum.d());
+        hipLaunchKernelGGL(tv2_long_mean_kernel, pgrid, block, 0, s, dsum.d(), n, gx, glam);
+        PTV_HIP(hipGetLastError());
+        return;
+    }
+    Scratch zh(sizeof(double) * (size_t)nn), zq(sizeof(double) * (size_t)nn), w(sizeof(double) * (size_t)nn),
+        amap(sizeof(double) * 2 * (size_t)blocks), partial(sizeof(double) * (size_t)blocks), partial2(sizeof(double) * (size_t)blocks),
+        kap(sizeof(double));
+    LongArgs p{g, zh.d(), w.d(), amap.d(), partial.d(), nn, 0.0, 1.0};
+    long_set_mu(p, mu);
+    // zh: forward elimination of D g (PASS 0 reads its right-hand side through p.y)
+    hipLaunchKernelGGL(tv2_long_reduce_kernel<0>, grid, block, 0, s, p);
+    hipLaunchKernelGGL(tv2_long_scan_kernel, dim3(1), block, 0, s, p, blocks);
+    hipLaunchKernelGGL(tv2_long_apply_kernel<0>, grid, block, 0, s, p);
+    // zq: the same of D y, with both dot products
+    p.y = y;
+    p.z = zq.d();
+    p.zh = zh.d();
+    p.partial2 = partial2.d();
+    hipLaunchKernelGGL(tv2_long_reduce_kernel<4>, grid, block, 0, s, p);
+    hipLaunchKernelGGL(tv2_long_scan_kernel, dim3(1), block, 0, s, p, blocks);
+    hipLaunchKernelGGL(tv2_long_apply_kernel<4>, grid, block, 0, s, p);
+    hipLaunchKernelGGL(tv2_long_kappa_kernel, dim3(1), block, 0, s, partial.d(), partial2.d(), blocks, mu, lam, kap.d(), glam);
+    // w: backward substitution of zh - kappa zq ; gx = g - D'w
+    p.kap = kap.d();
+    hipLaunchKernelGGL(tv2_long_reduce_kernel<5>, grid, block, 0, s, p);
+    hipLaunchKernelGGL(tv2_long_scan_kernel, dim3(1), block, 0, s, p, blocks);
+    hipLaunchKernelGGL(tv2_long_apply_kernel<5>, grid, block, 0, s, p);
+    hipLaunchKernelGGL(tv2_long_primal_kernel, pgrid, block, 0, s, g, w.d(), gx, n, 1);
+    PTV_HIP(hipGetLastError());
 }
 
 }  // namespace
 
-void tv2_fibres(const double *in, double *out, const int *ns, int nds, int dim, double lam, hipStream_t s) {
-    long n = 1;
-    for (int i = 0; i < nds; i++) n *= ns[i];
-    if (n <= 0) return;
-    const size_t bytes = sizeof(double) * (size_t)n;
-    FibreGeom g = fibres_along(ns, nds, dim);
+bool tv2_long_route(const FibreGeom &g, double lam) {
     // A handful of long contiguous fibres (a single signal through tv2_1d / TV(p = 2)): the solves run parallel inside the fibre,
     // one fibre after the other -- ~14 launches and two host round trips per Newton iteration, about a millisecond per fibre --
     // so only where that beats one lane per fibre, whose time grows with the fibre LENGTH (~1 us per sample: 0.2 s at 2 x 10^5)
     // whatever the count: count <= len / 2048 (8 fibres of 16 384 samples, 14 of 30 000; 48 of 16 384 stay lane-per-fibre), at most 32.
     const long long_max = g.len / 2048 < 32 ? g.len / 2048 : 32;
-    if (g.inc == 1 && g.count <= long_max && g.len >= kLongMinLen && (g.len - 1 + kLongBlock - 1) / kLongBlock <= kLongMaxBlocks && lam > 0.0) {
-        for (long j = 0; j < g.count; j++) tv2_long_fibre(in + j * g.len, out + j * g.len, g.len, lam, s);
+    return g.inc == 1 && g.count <= long_max && g.len >= kLongMinLen && (g.len - 1 + kLongBlock - 1) / kLongBlock <= kLongMaxBlocks && lam > 0.0;
+}
+
+void tv2_long_fibres_vjp(const double *y, const double *mu, const double *g, double *gx, double *glam, const FibreGeom &geo, double lam,
+                         hipStream_t s) {
+    std::vector<double> mus((size_t)geo.count);   // the multipliers decide theta, which the host computes
+    PTV_HIP(hipMemcpyAsync(mus.data(), mu, sizeof(double) * mus.size(), hipMemcpyDeviceToHost, s));
+    PTV_HIP(hipStreamSynchronize(s));
+    for (long j = 0; j < geo.count; j++)
+        tv2_long_fibre_vjp(y + j * geo.len, mus[(size_t)j], g + j * geo.len, gx + j * geo.len, glam ? glam + j : nullptr, geo.len, lam, s);
+}
+
+void tv2_fibres(const double *in, double *out, const int *ns, int nds, int dim, double lam, hipStream_t s, double *mu) {
+    long n = 1;
+    for (int i = 0; i < nds; i++) n *= ns[i];
+    if (n <= 0) return;
+    const size_t bytes = sizeof(double) * (size_t)n;
+    FibreGeom g = fibres_along(ns, nds, dim);
+    if (tv2_long_route(g, lam)) {
+        std::vector<double> mus((size_t)g.count);
+        for (long j = 0; j < g.count; j++) mus[(size_t)j] = tv2_long_fibre(in + j * g.len, out + j * g.len, g.len, lam, s);
         count_event(CNT_TV2_LONG_FIBRES, g.count);
+        if (mu) {
+            PTV_HIP(hipMemcpyAsync(mu, mus.data(), sizeof(double) * mus.size(), hipMemcpyHostToDevice, s));
+            PTV_HIP(hipStreamSynchronize(s));   // (mus leaves scope)
+        }
         return;
     }
     Scratch d(bytes), z(bytes), u(bytes);   // (the long path above brings its own, fibre-sized)
@@ -423,13 +554,13 @@ void tv2_fibres(const double *in, double *out, const int *ns, int nds, int dim, 
         Scratch tin(bytes), tout(bytes);
         slab_transpose(in, tin.d(), g.len, g.count, 1, s);
         const FibreGeom gt{g.count, g.len, g.count};
-        const Tv2Args a{tin.d(), tout.d(), d.d(), z.d(), u.d(), lam};
+        const Tv2Args a{tin.d(), tout.d(), d.d(), z.d(), u.d(), lam, mu};   // (fibre j of the transposed array is fibre j)
         hipLaunchKernelGGL(tv2_fibres_kernel, dim3((unsigned)((gt.count + 63) / 64)), dim3(64), 0, s, a, gt);
         PTV_HIP(hipGetLastError());
         slab_transpose(tout.d(), out, g.count, g.len, 1, s);
         return;
     }
-    const Tv2Args a{in, out, d.d(), z.d(), u.d(), lam};
+    const Tv2Args a{in, out, d.d(), z.d(), u.d(), lam, mu};
     hipLaunchKernelGGL(tv2_fibres_kernel, dim3((unsigned)((g.count + 63) / 64)), dim3(64), 0, s, a, g);
     PTV_HIP(hipGetLastError());
 }

@@ -1,4 +1,4 @@
-// tv2.hpp -- batched exact 1-D TV-L2 prox over fibres (tv2.hip).
+// tv2.hpp -- batched exact 1-D TV-L2 prox over fibres (tv2.hip) and its derivative (tv2_vjp.hip).
 #pragma once
 
 #include "common.hpp"
@@ -6,7 +6,23 @@
 namespace ptv {
 
 // out = argmin 1/2 ||x - in||^2 + lam ||Dx||_2 along dimension `dim` of every fibre of the N-D column-major array.
-// `in` and `out` must be distinct arrays.
-void tv2_fibres(const double *in, double *out, const int *ns, int nds, int dim, double lam, hipStream_t s);
+// `in` and `out` must be distinct arrays.  mu (device, or null): the multiplier of every fibre, one value per fibre in the column-major
+// order of the array with `dim` removed -- exactly 0.0 where the dual lies inside the ball (out is the mean), for ns[dim] == 1 and for
+// lam <= 0 (and where the first Newton step from mu = 0 is rejected: active by a rounding margin, the kink).  With mu == nullptr the
+// call is what it was without the argument, bit for bit.
+void tv2_fibres(const double *in, double *out, const int *ns, int nds, int dim, double lam, hipStream_t s, double *mu = nullptr);
+
+// The derivative of that prox applied to g: y and mu are what tv2_fibres returned for the same ns / dim / lam.
+// gx (may be g itself; otherwise no array may overlap another) = J g with J = dy/dx, symmetric; glam (device, one per fibre, or null)
+// the gradient in lam.  No atomics.
+void tv2_fibres_vjp(const double *y, const double *mu, const double *g, double *gx, double *glam, const int *ns, int nds, int dim,
+                    double lam, hipStream_t s);
+
+// ---- shared by the two units ----
+// whether fibres of this geometry go through the parallel-inside-the-fibre path (tv2_long_*) -- the forward and the derivative agree
+bool tv2_long_route(const FibreGeom &g, double lam);
+// the derivative along that path (tv2.hip: it reuses the forward's reduce / scan / apply kernels); contiguous fibres only
+void tv2_long_fibres_vjp(const double *y, const double *mu, const double *g, double *gx, double *glam, const FibreGeom &geo, double lam,
+                         hipStream_t s);
 
 }  // namespace ptv

@@ -423,6 +423,72 @@ def tvgen_vjp(x, g, ws, ds, iters, method=None, need_glam=False, need_y=False, t
     return gx, glam, y
 
 
+def _per_fibre_empty(shape, dim, device):
+    """float64 tensor with the shape of an array without its dimension `dim`, column-major (0-d for a 1-D array)."""
+    rest = tuple(s for i, s in enumerate(shape) if i != dim)
+    if not rest:
+        return torch.empty((), device=device, dtype=torch.float64)
+    return colmajor_empty(rest, device=device)
+
+
+def tv2_fibres(x, w, dim, out=None, return_mu=False):
+    """Batched exact 1-D TV-L2 prox (penalty ``w * ||diff||_2`` per fibre) of every fibre of `x` along 0-based `dim`.  With `return_mu`
+    returns (y, mu): mu, the shape of `x` without `dim`, holds every fibre's multiplier -- exactly 0 where the prox is the fibre's mean
+    (the dual lies inside the ball), for a dimension of extent 1 and for w <= 0; ``||diff(y)|| / w`` otherwise.  tv2_fibres_vjp needs it:
+    the case cannot be read off `y` in floating point."""
+    _check(x, "x")
+    y = _out(out, x)
+    if not 0 <= int(dim) < x.dim():
+        raise ValueError(f"dim {dim} out of range for a {x.dim()}-D array")
+    dim = int(dim)
+    ns = np.array(x.shape, dtype=np.int32)
+    mu = _per_fibre_empty(x.shape, dim, x.device) if return_mu else None
+    with torch.cuda.device(x.device):
+        lib = _lib.require_device()
+        lib.proxtv_tv2_fibres_dev(x.data_ptr(), y.data_ptr(), mu.data_ptr() if return_mu and mu.numel() else 0, ns.ctypes.data, x.dim(),
+                                  dim, float(w), _stream(x.device))
+    _lib.check("device.tv2_fibres")
+    return (y, mu) if return_mu else y
+
+
+def tv2_fibres_vjp(y, mu, g, w, dim, need_glam=False, out=None):
+    """The derivative of ``y, mu = tv2_fibres(x, w, dim, return_mu=True)`` applied to `g`: returns gx, or (gx, glam) with `need_glam`.
+
+    Per fibre, with M = tridiag(-1, 2 + mu, -1), D the difference matrix and h = D g: where mu > 0, p = M^-1 h, q = M^-1 (D y),
+    kappa = h'q / (D y)'q, gx = g - D'(p - kappa q) and glam = -mu w kappa; where mu == 0, gx is the mean of g and glam = 0.  The
+    Jacobian is symmetric, so this is the VJP and the JVP in x.  glam holds one value per fibre (the shape of `mu`); for one w shared by
+    all fibres d/dw is ``glam.sum()``.  At the kink the prox is not differentiable and the branch the forward took (`mu`) is what comes
+    out (include/proxtv_amd.h).  A `g` in another layout is copied; `out` may be `g`."""
+    _check(y, "y")
+    if not 0 <= int(dim) < y.dim():
+        raise ValueError(f"dim {dim} out of range for a {y.dim()}-D array")
+    dim = int(dim)
+    rest = tuple(s for i, s in enumerate(y.shape) if i != dim)
+    if not (isinstance(mu, torch.Tensor) and mu.is_cuda and mu.dtype == torch.float64 and tuple(mu.shape) == rest
+            and (mu.dim() == 0 or _is_colmajor(mu))):
+        raise ValueError(f"mu: expected a column-major float64 CUDA tensor of shape {rest} (tv2_fibres(..., return_mu=True))")
+    if mu.device != y.device:
+        raise ValueError(f"mu: lives on {mu.device}, the input on {y.device}")
+    if not (isinstance(g, torch.Tensor) and g.is_cuda and g.dtype == torch.float64):
+        raise ValueError("g: expected a float64 CUDA tensor")
+    if g.device != y.device:
+        raise ValueError(f"g: lives on {g.device}, the input on {y.device}")
+    if tuple(g.shape) != tuple(y.shape):
+        raise ValueError(f"g: shape {tuple(g.shape)}, expected {tuple(y.shape)}")
+    if not _is_colmajor(g):
+        g = to_colmajor(g)
+    gx = _out(out, y)
+    ns = np.array(y.shape, dtype=np.int32)
+    glam = _per_fibre_empty(y.shape, dim, y.device) if need_glam else None
+    ptr = lambda t: t.data_ptr() if t is not None and t.numel() else 0   # noqa: E731
+    with torch.cuda.device(y.device):
+        lib = _lib.require_device()
+        lib.proxtv_tv2_fibres_vjp_dev(ptr(y), ptr(mu), ptr(g), ptr(gx), ptr(glam), ns.ctypes.data, y.dim(), dim, float(w),
+                                      _stream(y.device))
+    _lib.check("device.tv2_fibres_vjp")
+    return (gx, glam) if need_glam else gx
+
+
 def tv1_fibres_dof(y, dim):
     """Segments of every fibre of ``y = tv1_fibres(x, w, dim)`` along `dim` (int32, the shape of `y` without `dim`): the trace of the
     prox's Jacobian, i.e. the degrees of freedom SURE needs.  One pass over `y`; nothing else is computed."""
