@@ -291,9 +291,8 @@ int proxtv_DR2_TV_vjp_dev(size_t M, size_t N, size_t B, const double *unary, dou
    proxtv_tv1_fibres_vjp_dev's segmented means sweep by sweep, last iteration first, with the pointwise work of the reverse recurrence
    inside those kernels.  What comes out is the derivative of the `iters`-step recurrence.  Limits: the dependence of the iteration count
    on the data through the stopping rule is NOT differentiated; the step rule and its two limits (kinks; the absolute 4e-10) are
-   proxtv_tv1_fibres_vjp_dev's; the forward agrees with the fused solve to rounding, not bit for bit.  Per-edge weight maps and TV-L2 terms
-   are not covered (there is no `norms` argument; the TV-L2 fibre prox alone is differentiated by proxtv_tv2_fibres_vjp_dev, from which
-   such a loop can be composed).  A total size of 0: returns 1, nothing is written.  iters < 1, which = 0 with npen > 2,
+   proxtv_tv1_fibres_vjp_dev's; the forward agrees with the fused solve to rounding, not bit for bit.  Per-edge weight maps are not
+   covered; TV-L2 terms are, by proxtv_PD_TVp_vjp_dev below (this entry has no `norms` argument: every term is TV-L1).  A total size of 0: returns 1, nothing is written.  iters < 1, which = 0 with npen > 2,
    a dimension out of range, a missing y / g / gy, any overlap except gy == g, or a tape beyond the cap: returns 0 with proxtv_last_error
    set and nothing written.  No atomics: the same call gives the same bits.  Synchronises the stream; returns 1 on success. */
 int proxtv_PD_TV_vjp_dev(int which /*0: PD2_TV, 1: PD_TV*/, const double *y, const double *lambdas /*host, as the forward takes them*/,
@@ -389,6 +388,31 @@ int proxtv_tv2_fibres_vjp_dev(const double *y, const double *mu, const double *g
                               void *stream);
 int proxtv_PD_TVp_dev(int which, const double *y, const double *lambdas_scaled, const double *norms, const double *dims,
                       double *x, double *info, const int *ns, int nds, int npen, int maxIters, void *stream);
+
+/* The derivatives of proxtv_DR2_TVp_dev and of proxtv_PD_TVp_dev (which = 0 / 1): proxtv_DR2_TV_vjp_tape_dev and proxtv_PD_TV_vjp_tape_dev
+   with a norm in {1, 2} per direction / per term.  Arguments, conventions and limits are those two calls': returns 1 on success, 0 with
+   proxtv_last_error set and nothing written on a bad argument; overlap only as gU == g / gy == g; an empty array returns 1; glam for
+   which = 1 is in the lambdas as passed; `iters` is the forward's reported count.  A norm outside {1, 2}: returns 0 with the error set.
+   The recurrences are the same ones; a TV-L1 sweep is differentiated by its segmented mean as before, a TV-L2 sweep by
+   proxtv_tv2_fibres_vjp_dev's two solves, with the pointwise work of the reverse recurrence inside that kernel for fibres along a
+   dimension >= 1 (dimension-0 fibres and fibres of >= 16384 samples: the plain kernel and one pointwise pass).  With every norm 1, or
+   norms == NULL, the result is the bits of the TV-L1 call.
+   The Douglas-Rachford entry takes one uniform image: TV-L2 has no per-edge weights and proxtv_DR2_TVp_dev has no batch.
+     glam        HOST double[2] (DR: d/dW1, d/dW2) / double[npen], or NULL.  For a TV-L2 term it is the sum over the fibres of
+                 proxtv_tv2_fibres_vjp_dev's glam, in sum_to's fixed order.
+   The kink: where a TV-L2 fibre's forward sweep took the mu = 0 branch (its dual inside the ball, or active by less than a Newton step),
+   that branch is what is differentiated -- the rule of proxtv_tv2_fibres_vjp_dev, sweep by sweep.
+   The tape.  A TV-L1 sweep keeps its float64 output (tape = 0) or its step codes (tape = 1) as before.  A TV-L2 sweep keeps its float64
+   output AND its multipliers, one double per fibre, under either tape: its derivative reads D y itself.  Bytes held against the pool's
+   cap, summed over the directions / terms d, with n the array's size, K the sweeps per term (DR: maxit + 1; PD: iters; PD2 with one
+   term: 1), words_d = proxtv_tv1_steps_words along d and fibres_d = n / ns[d]:
+       TV-L1, tape = 0:  8 K n          TV-L1, tape = 1:  8 n + 4 K words_d          TV-L2, either tape:  8 K (n + fibres_d)
+   Every result is the same bits for both tapes.  No atomics: the same call gives the same bits. */
+int proxtv_DR2_TVp_vjp_dev(size_t M, size_t N, const double *unary, double W1, double W2, double norm1, double norm2, const double *g,
+                           double *s /*or NULL*/, double *gU, double *glam /*host double[2], or NULL*/, int maxit, int tape, void *stream);
+int proxtv_PD_TVp_vjp_dev(int which, const double *y, const double *lambdas, const double *norms /*host, or NULL*/, const double *dims,
+                          const int *ns, int nds, int npen, int iters, const double *g, double *x /*or NULL*/, double *gy /*may be g*/,
+                          double *glam /*host, or NULL*/, int tape, void *stream);
 
 /* Timing hook for bench.py: average device time in milliseconds of the `which`-th kernel family
    over the last solve (0 = column sweep, 1 = row sweep, 2 = everything else), measured with

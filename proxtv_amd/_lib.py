@@ -93,6 +93,10 @@ SIGNATURES = {
     "proxtv_DR2_TVp_dev": (C.c_int, [C.c_size_t, C.c_size_t, _dp, C.c_double, C.c_double, C.c_double, C.c_double, _dp, C.c_int,
                                      _dp, C.c_void_p]),
     "proxtv_PD_TVp_dev": (C.c_int, [C.c_int, _dp, _dp, _dp, _dp, _dp, _dp, _ip, C.c_int, C.c_int, C.c_int, C.c_void_p]),
+    "proxtv_DR2_TVp_vjp_dev": (C.c_int, [C.c_size_t, C.c_size_t, _dp, C.c_double, C.c_double, C.c_double, C.c_double, _dp, _dp, _dp, _dp,
+                                         C.c_int, C.c_int, C.c_void_p]),
+    "proxtv_PD_TVp_vjp_dev": (C.c_int, [C.c_int, _dp, _dp, _dp, _dp, _ip, C.c_int, C.c_int, C.c_int, _dp, _dp, _dp, _dp, C.c_int,
+                                        C.c_void_p]),
     "proxtv_last_fixups": (C.c_long, []),
     "proxtv_chunk_mode": (C.c_int, []),
     "proxtv_debug_trace": (C.c_long, [C.c_void_p, C.c_long]),

@@ -13,10 +13,14 @@ saved, and backward is ONE device.dr2_vjp call, which replays the recurrence on 
 N-D entry tvgen is differentiated the same way through its two Dykstra loops ('pd2' / 'pd'): forward is the fused device.tvgen, backward
 ONE device.tvgen_vjp call with the iteration count the forward reported.  The other solvers (PDR, Yang, ...) are not
 differentiated: compose them from tv1_fibres and torch's pointwise operations.  The TV-L2 fibre prox has its own derivative:
-tv2_fibres(x, w, dim) is device.tv2_fibres with ONE device.tv2_fibres_vjp call as backward; TV-L2 terms inside the solver
-derivatives are not covered -- compose such loops from tv1_fibres and tv2_fibres.
+tv2_fibres(x, w, dim) is device.tv2_fibres with ONE device.tv2_fibres_vjp call as backward.  TV-L2 terms inside the two
+differentiated solver families are covered too: tvp_2d(x, w_col, w_row, p_col, p_row) is device.tvp_2d with ONE
+device.dr2_vjp(..., p_col=, p_row=) call as backward, and tvgen(..., ps=[...]) is device.tvgen(..., ps=) with ONE
+device.tvgen_vjp(..., ps=) call; every p is 1 or 2.  At a TV-L2 fibre's kink the branch the forward sweep took is differentiated.
 
     y = autograd.tvgen(x, [w0, w1, w2], [1, 2, 3])   # a volume; every w a float or a 0-d float64 tensor
+    y = autograd.tvgen(x, [w0, w1, w2], [1, 2, 3], ps=[1, 2, 1])
+    y = autograd.tvp_2d(x, w_col, w_row, 1, 2)
 
 Every function takes ``tape="outputs"`` (the default) or ``tape="steps"``: what is kept for the reverse sweeps.  With "steps",
 tv1_fibres saves the 2-bit step codes of its output (device.tv1_fibres_steps: an int32 tensor of 1/32 of y's bytes) in the graph instead
@@ -179,17 +183,58 @@ def tv1_2d_batch(xs, w, max_iters=0, tape="outputs"):
     return _DR2.apply(xs, w, w, int(max_iters), False, tape)
 
 
+class _DR2p(torch.autograd.Function):
+    """x, then the two uniform penalties (0-d tensors / floats); the norms, max_iters and tape ride in `spec`."""
+
+    @staticmethod
+    def forward(ctx, x, w_col, w_row, spec):
+        p_col, p_row, max_iters, tape = spec
+        xd = _colmajor(x.detach())
+        y, _ = device.tvp_2d(xd, float(w_col), float(w_row), p_col, p_row, max_iters)
+        ctx.save_for_backward(xd)
+        ctx.lams, ctx.spec = (float(w_col), float(w_row)), spec
+        ctx.lam_devices = tuple(w.device if isinstance(w, torch.Tensor) else None for w in (w_col, w_row))
+        return y
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, gy):
+        (x,) = ctx.saved_tensors
+        p_col, p_row, max_iters, tape = ctx.spec
+        need_x, need_col, need_row = ctx.needs_input_grad[:3]
+        gx, _, _, glam, _ = device.dr2_vjp(x, gy, ctx.lams[0], ctx.lams[1], max_iters, need_gw="sums" if need_col or need_row else False,
+                                           tape=tape, p_col=p_col, p_row=p_row)
+        gc = gr = None
+        if glam is not None:
+            gc, gr = (None if d is None else torch.tensor(float(v), dtype=torch.float64, device=d) for v, d in zip(glam, ctx.lam_devices))
+        return (gx if need_x else None), (gc if need_col else None), (gr if need_row else None), None
+
+
+def tvp_2d(x, w_col, w_row, p_col, p_row, max_iters=0, tape="outputs"):
+    """``device.tvp_2d(x, w_col, w_row, p_col, p_row, max_iters)[0]`` (Douglas-Rachford with a TV-L1 or TV-L2 penalty per direction, p in
+    {1, 2}) with a graph behind it: differentiable in x and in w_col / w_row where they are 0-d float64 tensors (the gradient comes back on
+    that tensor's device; one tensor for both receives the sum).  The result is bit for bit device.tvp_2d's; backward is ONE
+    device.dr2_vjp call.  When nothing asks for a gradient this IS device.tvp_2d."""
+    _scalar_penalty(w_col, "w_col")
+    _scalar_penalty(w_row, "w_row")
+    device._tape(tape)
+    device._norms((p_col, p_row), 2, "p_col / p_row")
+    if not _wants(x, w_col, w_row):
+        return device.tvp_2d(x, float(w_col), float(w_row), p_col, p_row, max_iters)[0]
+    return _DR2p.apply(x, w_col, w_row, (float(p_col), float(p_row), int(max_iters), tape))
+
+
 class _TVGen(torch.autograd.Function):
-    """x, then the penalties one by one (0-d tensors / floats); ds, max_iters, method and tape ride in `spec`."""
+    """x, then the penalties one by one (0-d tensors / floats); ds, max_iters, method, tape and the norms ride in `spec`."""
 
     @staticmethod
     def forward(ctx, x, spec, *ws):
-        ds, max_iters, method, tape = spec
+        ds, max_iters, method, tape, ps = spec
         xd = _colmajor(x.detach())
         lams = [float(w) for w in ws]
-        y, info = device.tvgen(xd, lams, ds, max_iters, method)
+        y, info = device.tvgen(xd, lams, ds, max_iters, method, ps=ps)
         ctx.save_for_backward(xd)
-        ctx.lams, ctx.ds, ctx.method, ctx.tape = lams, ds, method, tape
+        ctx.lams, ctx.ds, ctx.method, ctx.tape, ctx.ps = lams, ds, method, tape, ps
         ctx.iters = int(info[0])
         ctx.lam_devices = tuple(w.device if isinstance(w, torch.Tensor) else None for w in ws)
         return y
@@ -202,25 +247,27 @@ class _TVGen(torch.autograd.Function):
         if x.numel() == 0 or ctx.iters < 1:      # (nothing was iterated: the result does not depend on anything)
             gx, glam = torch.zeros_like(x), [0.0] * len(ctx.lams)
         else:
-            gx, glam, _ = device.tvgen_vjp(x, gy, ctx.lams, ctx.ds, ctx.iters, ctx.method, need_glam=any(need_ws), tape=ctx.tape)
+            gx, glam, _ = device.tvgen_vjp(x, gy, ctx.lams, ctx.ds, ctx.iters, ctx.method, need_glam=any(need_ws), tape=ctx.tape, ps=ctx.ps)
         gws = tuple(torch.tensor(float(glam[i]), dtype=torch.float64, device=ctx.lam_devices[i]) if need else None
                     for i, need in enumerate(need_ws))
         return ((gx if need_x else None), None) + gws
 
 
-def tvgen(x, ws, ds, max_iters=0, method=None, tape="outputs"):
+def tvgen(x, ws, ds, max_iters=0, method=None, tape="outputs", ps=None):
     """``device.tvgen(x, ws, ds, max_iters, method)[0]`` with a graph behind it: differentiable in x and in every entry of `ws` that is a
     0-d float64 tensor (its gradient comes back on that tensor's device; a tensor that appears in several entries receives the sum).
     method: None (tvgen's dispatch), 'pd2' or 'pd'; 'pdr' and 'yang' raise NotImplementedError when a gradient is asked for.  The result
     is bit for bit device.tvgen's; when nothing asks for a gradient this IS device.tvgen.  Backward differentiates the iterations the
-    forward ran (its info[0]), not the dependence of their number on the data."""
+    forward ran (its info[0]), not the dependence of their number on the data.  ps (one of {1, 2} per term, or None = all 1): the norm
+    of every term's penalty, as device.tvgen takes it."""
     ws = list(ws)
+    ps = None if ps is None else tuple(float(p) for p in device._norms(ps, len(ws)))
     for i, w in enumerate(ws):
         _scalar_penalty(w, f"ws[{i}]")
     device._tape(tape)
     if not _wants(x, *ws):
-        return device.tvgen(x, [float(w) for w in ws], ds, max_iters, method)[0]
+        return device.tvgen(x, [float(w) for w in ws], ds, max_iters, method, ps=ps)[0]
     m = method if method is not None else ("pd2" if len(ws) == 2 else "pd")
     if m not in ("pd2", "pd"):
         raise NotImplementedError(f"method {m!r} has no derivative (autograd.tvgen covers 'pd2' and 'pd')")
-    return _TVGen.apply(x, (tuple(float(d) for d in ds), int(max_iters), method, tape), *ws)
+    return _TVGen.apply(x, (tuple(float(d) for d in ds), int(max_iters), method, tape, ps), *ws)

@@ -732,9 +732,11 @@ int proxtv_tv1_fibres_vjp_steps_dev(const unsigned *steps, const double *g, doub
 // proxtv_DR2_TV_vjp_dev is the tape = 0 call of proxtv_DR2_TV_vjp_tape_dev
 static int dr2_vjp_entry(const char *who, size_t M, size_t N, size_t B, const double *unary, double W1, double W2, const double *W1m,
                          const double *W2m, const double *g, double *s, double *gU, double *gW1, double *gW2, double *glam, int maxit, int tape,
-                         void *stream) {
+                         void *stream, double norm1 = 1.0, double norm2 = 1.0) {
     return guarded(who, nullptr, 1, [&] {
         if (tape != 0 && tape != 1) reject("tape: 0 (sweep outputs) or 1 (step codes)");
+        const double nrm[2] = {norm1, norm2};
+        check_norms(nrm, 2);
         const size_t n = M * N * B;
         if (n == 0) return;
         if (M > 0x7fffffffu || N > 0x7fffffffu || B > 65535u) reject("image extents beyond 2^31 - 1 or more than 65535 images");
@@ -756,14 +758,14 @@ static int dr2_vjp_entry(const char *who, size_t M, size_t N, size_t B, const do
                 }
             }
         }
-        const size_t need = dr2_vjp_tape_bytes(M, N, B, maxit, tape);
+        const size_t need = dr2_vjp_tape_bytes(M, N, B, maxit, tape, norm1, norm2);
         if (need > pool_cap_bytes()) {
             set_error("the tape of sweep outputs needs %zu bytes, the scratch pool is capped at %zu (PROXTV_POOL_CAP_MB)", need, pool_cap_bytes());
             throw HipFailure{hipErrorOutOfMemory};
         }
         hipStream_t st = pick(stream);
         SolveScope scope(st);
-        dr2_vjp(M, N, B, unary, W1, W2, W1m, W2m, g, s, gU, gW1, gW2, glam, maxit, tape, st);
+        dr2_vjp(M, N, B, unary, W1, W2, W1m, W2m, g, s, gU, gW1, gW2, glam, maxit, tape, st, norm1, norm2);
         scope.finish();
     });
 }
@@ -781,13 +783,14 @@ int proxtv_DR2_TV_vjp_tape_dev(size_t M, size_t N, size_t B, const double *unary
 
 // proxtv_PD_TV_vjp_dev is the tape = 0 call of proxtv_PD_TV_vjp_tape_dev
 static int pd_vjp_entry(const char *who, int which, const double *y, const double *lambdas, const double *dims, const int *ns, int nds, int npen,
-                        int iters, const double *g, double *x, double *gy, double *glam, int tape, void *stream) {
+                        int iters, const double *g, double *x, double *gy, double *glam, int tape, void *stream, const double *norms = nullptr) {
     return guarded(who, nullptr, 1, [&] {
         if (tape != 0 && tape != 1) reject("tape: 0 (sweep outputs) or 1 (step codes)");
         if (which != 0 && which != 1) reject("which: 0 (PD2_TV) or 1 (PD_TV)");
         if (iters < 1) reject("iters: the iteration count of the forward solve (info[0]), at least 1");
         if (npen < 1) reject("at least one penalty term is required");
         if (which == 0 && npen > 2) reject("PD2 works with 1 or 2 penalties");
+        if (norms && !check_norms(norms, npen)) norms = nullptr;   // (every term TV-L1: the call without norms)
         check_dims(dims, npen, nds);
         const size_t n = (size_t)total(ns, nds);
         if (n == 0) return;
@@ -806,14 +809,14 @@ static int pd_vjp_entry(const char *who, int which, const double *y, const doubl
                 }
             }
         }
-        const size_t need = pd_vjp_tape_bytes(which, dims, ns, nds, npen, iters, tape);
+        const size_t need = pd_vjp_tape_bytes(which, dims, ns, nds, npen, iters, tape, norms);
         if (need > pool_cap_bytes()) {
             set_error("the tape of sweep outputs needs %zu bytes, the scratch pool is capped at %zu (PROXTV_POOL_CAP_MB)", need, pool_cap_bytes());
             throw HipFailure{hipErrorOutOfMemory};
         }
         hipStream_t st = pick(stream);
         SolveScope scope(st);
-        pd_vjp(which, y, lambdas, dims, ns, nds, npen, iters, g, x, gy, glam, tape, st);
+        pd_vjp(which, y, lambdas, dims, ns, nds, npen, iters, g, x, gy, glam, tape, st, norms);
         scope.finish();
     });
 }
@@ -826,6 +829,17 @@ int proxtv_PD_TV_vjp_dev(int which, const double *y, const double *lambdas, cons
 int proxtv_PD_TV_vjp_tape_dev(int which, const double *y, const double *lambdas, const double *dims, const int *ns, int nds, int npen, int iters,
                               const double *g, double *x, double *gy, double *glam, int tape, void *stream) {
     return pd_vjp_entry("proxtv_PD_TV_vjp_tape_dev", which, y, lambdas, dims, ns, nds, npen, iters, g, x, gy, glam, tape, stream);
+}
+
+int proxtv_DR2_TVp_vjp_dev(size_t M, size_t N, const double *unary, double W1, double W2, double norm1, double norm2, const double *g, double *s,
+                           double *gU, double *glam, int maxit, int tape, void *stream) {
+    return dr2_vjp_entry("proxtv_DR2_TVp_vjp_dev", M, N, 1, unary, W1, W2, nullptr, nullptr, g, s, gU, nullptr, nullptr, glam, maxit, tape, stream,
+                         norm1, norm2);
+}
+
+int proxtv_PD_TVp_vjp_dev(int which, const double *y, const double *lambdas, const double *norms, const double *dims, const int *ns, int nds,
+                          int npen, int iters, const double *g, double *x, double *gy, double *glam, int tape, void *stream) {
+    return pd_vjp_entry("proxtv_PD_TVp_vjp_dev", which, y, lambdas, dims, ns, nds, npen, iters, g, x, gy, glam, tape, stream, norms);
 }
 
 int proxtv_tvp_fibres_dev(const double *in, double *out, const int *ns, int nds, int dim, double lambda, double p,

@@ -35,18 +35,23 @@ void tv1_fibres_vjp_steps(const unsigned *steps, const double *g, double *gx, do
 // (dr2_vjp_tape_bytes; the caller checks it against pool_cap_bytes), then the reverse sweeps.  out / gW1 / gW2 / glam may be null; gU may
 // be g, no other overlap.  glam: HOST double[2 B], (sum gW1, sum gW2) per image.  Returns with the stream drained.
 // tape = 1: the sweeps write into two reused arrays and only the step codes of every output are kept (32 times less per output).
-size_t dr2_vjp_tape_bytes(size_t M, size_t N, size_t B, int maxit, int tape);
+// norm1 / norm2 in {1, 2}: a TV-L2 direction's sweeps keep their output and multipliers under either tape and are
+// differentiated by tv2_vjp.hip's write-out modes; it has no per-edge gradient (gW of that direction is ignored) and wants B == 1 and no
+// weight maps.  Both 1: the launches, and so the bits, of the call without the arguments.
+size_t dr2_vjp_tape_bytes(size_t M, size_t N, size_t B, int maxit, int tape, double norm1 = 1.0, double norm2 = 1.0);
 void dr2_vjp(size_t M, size_t N, size_t B, const double *unary, double W1, double W2, const double *W1m, const double *W2m, const double *g,
-             double *out, double *gU, double *gW1, double *gW2, double *glam, int maxit, int tape, hipStream_t s);
+             double *out, double *gU, double *gW1, double *gW2, double *glam, int maxit, int tape, hipStream_t s, double norm1 = 1.0,
+             double norm2 = 1.0);
 
 // the derivative of pd2 (which == 0; npen <= 2) / pd (which == 1) with TV-L1 terms (vjp.hip): runs `iters` iterations of the
 // unfused recurrence -- no stopping test, nothing read back -- with every sweep output kept in pool scratch (pd_vjp_tape_bytes; the caller
 // checks it against pool_cap_bytes), then the reverse sweeps.  lambdas / dims: host, as pd2 / pd take them.  x / glam may be null; gy may be
 // g, no other overlap.  glam: HOST double[npen], the gradient in `lambdas` as passed.  Returns with the stream drained.
 // tape = 1: step codes of every output, and one reused array per term.
-size_t pd_vjp_tape_bytes(int which, const double *dims, const int *ns, int nds, int npen, int iters, int tape);
+// norms (host, one of {1, 2} per term, or null = all 1): TV-L2 terms as for dr2_vjp; all 1: the launches of the call without the argument.
+size_t pd_vjp_tape_bytes(int which, const double *dims, const int *ns, int nds, int npen, int iters, int tape, const double *norms = nullptr);
 void pd_vjp(int which, const double *y, const double *lambdas, const double *dims, const int *ns, int nds, int npen, int iters, const double *g,
-            double *x, double *gy, double *glam, int tape, hipStream_t s);
+            double *x, double *gy, double *glam, int tape, hipStream_t s, const double *norms = nullptr);
 
 // out = prox along `dim` with the TV-L1 (norm 1: the sweep kernels) or TV-L2 (norm 2: tv2.hip) penalty; in != out
 void prox_fibres(const double *in, double *out, const int *ns, int nds, int dim, double lam, double norm, hipStream_t s);

@@ -18,6 +18,30 @@ void tv2_fibres(const double *in, double *out, const int *ns, int nds, int dim, 
 void tv2_fibres_vjp(const double *y, const double *mu, const double *g, double *gx, double *glam, const int *ns, int nds, int dim,
                     double lam, hipStream_t s);
 
+// The same derivative as one sweep of a solver's reverse recurrence (vjp.hip: dr2_vjp, pd_vjp).  With a = J g the modes are
+// vjp.hip's, a standing where the segmented mean stands there:
+//   TV2_VJP_PLAIN    gx = a                                                              (tv2_fibres_vjp, bit for bit)
+//   TV2_VJP_DR_ROW   g = gbar in place:  gU += a ;  c = 2 a - g ;  gx = g - a            (final: gU = a ;  c = a ;  gx = -a)
+//   TV2_VJP_DR_COL   gx += a
+//   TV2_VJP_PD2      g = D in place:     gx = a - g  (with gU: gU += a)                  (final: gx = a without gU ;  gU = a with it)
+//   TV2_VJP_PD       the cotangent is pi = fma(g, scale, -zeta), formed on load in both passes by that one fma (zeta == null: 0);
+//                    gx = zeta in place:  gx = zeta + a ;  gU += gx                       (final: gU = gx)
+// glam: one value per fibre, written, or accumulated with add_glam.  Every element is read and written by the lane that owns it.
+enum { TV2_VJP_PLAIN = 0, TV2_VJP_DR_ROW = 1, TV2_VJP_DR_COL = 2, TV2_VJP_PD2 = 3, TV2_VJP_PD = 4 };
+struct Tv2VjpEpi {
+    int mode = TV2_VJP_PLAIN;
+    double *gU = nullptr, *c = nullptr;
+    int final = 0;
+    int add_glam = 0;
+    const double *zeta = nullptr;
+    double scale = 0.0;
+};
+// Strided fibres (dim >= 1, and a single dimension-0 fibre) run the write-out inside the lane-per-fibre kernel.  Dimension-0 fibres (the
+// transposed route) and the long-fibre route run TV2_VJP_PLAIN into scratch and one pointwise kernel behind it (TV2_VJP_PD: one more in
+// front, which forms pi with the same fma).
+void tv2_fibres_vjp_epi(const double *y, const double *mu, const double *g, double *gx, double *glam, const int *ns, int nds, int dim,
+                        double lam, const Tv2VjpEpi &epi, hipStream_t s);
+
 // ---- shared by the two units ----
 // whether fibres of this geometry go through the parallel-inside-the-fibre path (tv2_long_*) -- the forward and the derivative agree
 bool tv2_long_route(const FibreGeom &g, double lam);

@@ -23,6 +23,11 @@
 //
 // The third part is the derivative of the two Dykstra loops behind tvgen (proxtv_PD_TV_vjp_dev), built the same way:
 // VJP_PD2 for the two-term loop, VJP_PD_SUMMARY / VJP_PD for the parallel one, whose cotangent is formed on load in phases A and C.
+//
+// All three loops take a norm in {1, 2} per direction / term (proxtv_DR2_TVp_vjp_dev, proxtv_PD_TVp_vjp_dev): every
+// reverse recurrence is linear in a = J g, whichever prox J belongs to.  A TV-L1 sweep keeps the launches described above; a TV-L2
+// sweep is tv2_fibres with its multipliers forward and tv2_vjp.hip's kernel with the same write-out mode in reverse (tape_prox /
+// tape_vjp), and SweepTape says what each keeps.
 #include "solvers.hpp"
 #include "vjpcore.hpp"
 
@@ -33,6 +38,7 @@
 
 #include "pointwise.hpp"
 #include "sweep.hpp"
+#include "tv2.hpp"
 
 namespace ptv {
 
@@ -468,15 +474,99 @@ __global__ __launch_bounds__(256) void dr_vjp_mean_term_kernel(double *gU, long 
     for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long)gridDim.x * 256) seg[i] += v;
 }
 
+// ---- what the forward keeps of one term's K sweeps ------------------------------------------------------------------------
+//   TV-L1, tape = 0   K outputs                                          8 K n bytes
+//   TV-L1, tape = 1   one array the sweeps reuse, K word arrays          8 n + 4 K words
+//   TV-L2, any tape   K outputs and K multiplier arrays (one double per fibre): the derivative reads D y itself     8 K (n + fibres)
+// Inside the one scratch block: every term's doubles, in the order of the terms, then every term's words.
+struct SweepTape {
+    bool l2 = false;
+    int K = 0, tape = 0;
+    size_t n = 0, fibres = 0, units = 0;   // samples ; fibres along the term's dimension ; step-code words of one output
+    double *out = nullptr, *mus = nullptr;
+    unsigned *words = nullptr;
+    size_t doubles() const { return l2 ? (size_t)K * (n + fibres) : (tape ? n : (size_t)K * n); }
+    size_t nwords() const { return (!l2 && tape) ? (size_t)K * units : 0; }
+    double *y(int k) const { return out + ((l2 || !tape) ? (size_t)k * n : 0); }
+    double *mu(int k) const { return l2 ? mus + (size_t)k * fibres : nullptr; }
+    unsigned *w(int k) const { return words ? words + (size_t)k * units : nullptr; }
+};
+
+SweepTape sweep_tape(const int *ns, int nds, int dim, double norm, int K, int tape) {
+    SweepTape t;
+    const FibreGeom geo = fibres_along(ns, nds, dim);
+    t.l2 = norm == 2;
+    t.K = K;
+    t.tape = tape;
+    if (geo.count <= 0 || geo.len <= 0) return t;
+    t.n = (size_t)geo.count * (size_t)geo.len;
+    t.fibres = (size_t)geo.count;
+    t.units = (size_t)vjp_units(geo);
+    return t;
+}
+
+size_t tape_bytes(const std::vector<SweepTape> &terms) {
+    size_t d = 0, w = 0;
+    for (const SweepTape &t : terms) {
+        d += t.doubles();
+        w += t.nwords();
+    }
+    return d * sizeof(double) + w * sizeof(unsigned);
+}
+
+void tape_carve(std::vector<SweepTape> &terms, double *block) {
+    double *d = block;
+    for (SweepTape &t : terms) {
+        t.out = d;
+        t.mus = t.l2 ? d + (size_t)t.K * t.n : nullptr;
+        d += t.doubles();
+    }
+    unsigned *w = reinterpret_cast<unsigned *>(d);
+    for (SweepTape &t : terms) {
+        t.words = t.nwords() ? w : nullptr;
+        w += t.nwords();
+    }
+}
+
+// sweep k of a term, forward: its output (and, TV-L2, its multipliers) where the tape keeps them
+void tape_prox(const double *in, const SweepTape &t, int k, const int *ns, int nds, int dim, double lam, const double *weights, hipStream_t s) {
+    if (t.l2) tv2_fibres(in, t.y(k), ns, nds, dim, lam, s, t.mu(k));
+    else      tv1_fibres(in, t.y(k), ns, nds, dim, lam, weights, s);
+}
+
+constexpr int tv2_mode_of(int mode) {
+    return mode == VJP_DR_ROW ? TV2_VJP_DR_ROW : mode == VJP_DR_COL ? TV2_VJP_DR_COL : mode == VJP_PD2 ? TV2_VJP_PD2
+         : mode == VJP_PD ? TV2_VJP_PD : TV2_VJP_PLAIN;
+}
+
+// ... and in reverse, a = J g with J that sweep's Jacobian and the write-out MODE: the segmented mean from the output or its words
+// (gw: per edge), or the TV-L2 derivative from the output and its multipliers (gw: per fibre)
+template <int MODE>
+void tape_vjp(const SweepTape &t, int k, const double *g, double *gx, double *gw, const int *ns, int nds, int dim, double lam, const FibreGeom &geo,
+              Summary *S, Resolved *R, const VjpEpi &epi, hipStream_t s) {
+    if (!t.l2) {
+        vjp_launch_taped<MODE>(t.y(k), t.w(k), g, gx, gw, geo, S, R, epi, s);
+        return;
+    }
+    Tv2VjpEpi e;
+    e.mode = tv2_mode_of(MODE);
+    e.gU = epi.gU;
+    e.c = epi.c;
+    e.final = epi.final;
+    e.add_glam = epi.add_gw;
+    e.zeta = epi.zeta;
+    e.scale = epi.scale;
+    tv2_fibres_vjp_epi(t.y(k), t.mu(k), g, gx, gw, ns, nds, dim, lam, e, s);
+}
+
 }  // namespace
 
-size_t dr2_vjp_tape_bytes(size_t M, size_t N, size_t B, int maxit, int tape) {
+// bytes = sum over the two directions d (n = M N B, K = maxit + 1):  TV-L1, tape 0: 8 K n ;  TV-L1, tape 1: 8 n + 4 K words_d ;
+// TV-L2: 8 K (n + fibres_d), fibres_0 = N B, fibres_1 = M B
+size_t dr2_vjp_tape_bytes(size_t M, size_t N, size_t B, int maxit, int tape, double norm1, double norm2) {
     if (maxit <= 0) maxit = MAX_ITERS_DR;
-    if (!tape) return 2 * ((size_t)maxit + 1) * sizeof(double) * M * N * B;
-    // step codes: a word array per sweep output, and the two arrays the sweeps write into
     const int ns[3] = {(int)M, (int)N, (int)B};
-    const size_t words = (size_t)tv1_steps_words(ns, 3, 0) + (size_t)tv1_steps_words(ns, 3, 1);
-    return ((size_t)maxit + 1) * words * sizeof(unsigned) + 2 * sizeof(double) * M * N * B;
+    return tape_bytes({sweep_tape(ns, 3, 0, norm1, maxit + 1, tape), sweep_tape(ns, 3, 1, norm2, maxit + 1, tape)});
 }
 
 // Forward: the recurrence of dr2_norms (solvers.hip) on B stacked images with the sweep outputs x1_k, x2_k kept, k = 0 .. maxit (the last
@@ -490,24 +580,26 @@ size_t dr2_vjp_tape_bytes(size_t M, size_t N, size_t B, int maxit, int tape) {
 // tape = 1: x1_k and x2_k are written into two arrays that every iteration reuses and encoded behind their sweep (vjp_encode); the
 // reverse loop is the same with the words of sweep k where y was.
 void dr2_vjp(size_t M, size_t N, size_t B, const double *unary, double W1, double W2, const double *W1m, const double *W2m, const double *g,
-             double *out, double *gU, double *gW1, double *gW2, double *glam, int maxit, int tape, hipStream_t s) {
+             double *out, double *gU, double *gW1, double *gW2, double *glam, int maxit, int tape, hipStream_t s, double norm1, double norm2) {
     const long n1 = (long)(M * N), n = n1 * (long)B;
+    const bool l2c = norm1 == 2, l2r = norm2 == 2;   // (a TV-L2 direction: one uniform image, no per-edge gradients)
+    if (l2c) gW1 = nullptr;
+    if (l2r) gW2 = nullptr;
     if (maxit <= 0) maxit = MAX_ITERS_DR;
     if (n == 0) return;
     const int ns[3] = {(int)M, (int)N, (int)B};
     const FibreGeom cols = fibres_along(ns, 3, 0), rows = fibres_along(ns, 3, 1);
-    const long e1 = (long)((M - 1) * N), e2 = (long)(M * (N - 1));   // edges per image
+    // what a direction's penalty gradient is summed from, per image: its edges (TV-L1) or its fibres (TV-L2)
+    const long e1 = l2c ? cols.count : (long)((M - 1) * N), e2 = l2r ? rows.count : (long)(M * (N - 1));
     const size_t bytes = sizeof(double) * (size_t)n;
 
-    Scratch kept(dr2_vjp_tape_bytes(M, N, B, maxit, tape)), t(bytes), v(bytes);
+    std::vector<SweepTape> kept_of{sweep_tape(ns, 3, 0, norm1, maxit + 1, tape), sweep_tape(ns, 3, 1, norm2, maxit + 1, tape)};
+    Scratch kept(tape_bytes(kept_of)), t(bytes), v(bytes);
     Scratch partials(sizeof(double) * kReduceBlocks * B), sums(sizeof(double) * 2 * B);
-    // tape = 0: 2 (maxit + 1) outputs ; tape = 1: the two live outputs, then per k the words of x1_k and of x2_k
-    const size_t wc = (size_t)vjp_units(cols), wr = (size_t)vjp_units(rows);
-    unsigned *const words = tape ? reinterpret_cast<unsigned *>(kept.d() + 2 * (size_t)n) : nullptr;
-    auto x1 = [&](int k) { return kept.d() + (tape ? 0 : (size_t)(2 * k) * (size_t)n); };
-    auto x2 = [&](int k) { return kept.d() + (tape ? (size_t)n : (size_t)(2 * k + 1) * (size_t)n); };
-    auto c1 = [&](int k) { return tape ? words + (size_t)k * (wc + wr) : nullptr; };
-    auto c2 = [&](int k) { return tape ? words + (size_t)k * (wc + wr) + wc : nullptr; };
+    tape_carve(kept_of, kept.d());
+    const SweepTape &tc = kept_of[0], &tr = kept_of[1];
+    auto x1 = [&](int k) { return tc.y(k); };
+    auto x2 = [&](int k) { return tr.y(k); };
     {   // seed of the geometry policy, like dr2: the image's edge statistics (the first array a sweep sees here is the constant t0)
         const int both[2] = {0, 1};
         const double *const wts[2] = {W1m, W2m};
@@ -517,14 +609,12 @@ void dr2_vjp(size_t M, size_t N, size_t B, const double *unary, double W1, doubl
     dr_fill(t.d(), n1, (long)B, sums.d(), 1.0, s);
     for (int k = 0; k <= maxit; k++) {
         const bool last = k == maxit;
-        tv1_fibres(t.d(), x1(k), ns, 3, 0, W1, W1m, s);
+        tape_prox(t.d(), tc, k, ns, 3, 0, W1, W1m, s);
         lincomb(v.d(), unary, 1.0, t.d(), -1.0, x1(k), last ? 1.0 : 2.0, nullptr, 0, n, s);
-        tv1_fibres(v.d(), x2(k), ns, 3, 1, W2, W2m, s);
+        tape_prox(v.d(), tr, k, ns, 3, 1, W2, W2m, s);
         if (!last) lincomb(t.d(), t.d(), 1.0, x1(k), -1.0, x2(k), 1.0, nullptr, 0, n, s);
-        if (tape) {
-            vjp_encode(x1(k), c1(k), cols, s);
-            vjp_encode(x2(k), c2(k), rows, s);
-        }
+        if (tc.w(k)) vjp_encode(x1(k), tc.w(k), cols, s);
+        if (tr.w(k)) vjp_encode(x2(k), tr.w(k), rows, s);
     }
     if (out) PTV_HIP(hipMemcpyAsync(out, x2(maxit), bytes, hipMemcpyDeviceToDevice, s));
 
@@ -543,8 +633,8 @@ void dr2_vjp(size_t M, size_t N, size_t B, const double *unary, double W1, doubl
         row.c = c;
         row.final = k == maxit;
         row.add_gw = col.add_gw = k != maxit;
-        vjp_launch_taped<VJP_DR_ROW>(x2(k), c2(k), row.final ? g : gbar, gbar, w2, rows, S.as<Summary>(), R.as<Resolved>(), row, s);
-        vjp_launch_taped<VJP_DR_COL>(x1(k), c1(k), c, gbar, w1, cols, S.as<Summary>(), R.as<Resolved>(), col, s);
+        tape_vjp<VJP_DR_ROW>(tr, k, row.final ? g : gbar, gbar, w2, ns, 3, 1, W2, rows, S.as<Summary>(), R.as<Resolved>(), row, s);
+        tape_vjp<VJP_DR_COL>(tc, k, c, gbar, w1, ns, 3, 0, W1, cols, S.as<Summary>(), R.as<Resolved>(), col, s);
     }
     sum_to(gbar, n1, (long)B, partials.d(), sums.d(), s);
     {
@@ -580,13 +670,21 @@ long total(const int *ns, int nds) {
 
 }  // namespace
 
-size_t pd_vjp_tape_bytes(int which, const double *dims, const int *ns, int nds, int npen, int iters, int tape) {
-    const size_t K = (which == 0 && npen == 1) ? 1 : (size_t)iters;   // (one term: every iteration repeats the first)
-    if (!tape) return K * (size_t)npen * sizeof(double) * (size_t)total(ns, nds);
-    // step codes: a word array per sweep output, and one array per term for the sweeps to write into
-    size_t words = 0;
-    for (int i = 0; i < npen; i++) words += (size_t)tv1_steps_words(ns, nds, (int)(dims[i] - 1));
-    return K * words * sizeof(unsigned) + (size_t)npen * sizeof(double) * (size_t)total(ns, nds);
+namespace {
+
+std::vector<SweepTape> pd_tapes(int which, const double *dims, const double *norms, const int *ns, int nds, int npen, int iters, int tape) {
+    const int K = (which == 0 && npen == 1) ? 1 : iters;   // (one term: every iteration repeats the first)
+    std::vector<SweepTape> terms;
+    for (int i = 0; i < npen; i++) terms.push_back(sweep_tape(ns, nds, (int)(dims[i] - 1), norms ? norms[i] : 1.0, K, tape));
+    return terms;
+}
+
+}  // namespace
+
+// bytes = sum over the terms i (n the array's size, K = iters, or 1 for which = 0 with one term):  TV-L1, tape 0: 8 K n ;
+// TV-L1, tape 1: 8 n + 4 K words_i ;  TV-L2: 8 K (n + fibres_i), fibres_i = n / ns[dims[i] - 1]
+size_t pd_vjp_tape_bytes(int which, const double *dims, const int *ns, int nds, int npen, int iters, int tape, const double *norms) {
+    return tape_bytes(pd_tapes(which, dims, norms, ns, nds, npen, iters, tape));
 }
 
 namespace {
@@ -597,8 +695,8 @@ struct TermGw {
     std::unique_ptr<Scratch> buf;
     double *d() const { return buf ? buf->d() : nullptr; }
 };
-void term_gw(TermGw &t, const FibreGeom &geo, bool wanted) {
-    t.edges = geo.count * (long)(geo.len - 1);
+void term_gw(TermGw &t, const FibreGeom &geo, bool wanted, bool l2 = false) {
+    t.edges = l2 ? geo.count : geo.count * (long)(geo.len - 1);   // (a TV-L2 sweep hands out one value per fibre)
     if (wanted && t.edges > 0) t.buf.reset(new Scratch(sizeof(double) * (size_t)t.edges));
 }
 // glam[i] = the sum of term i's per-edge gradients, in sum_to's fixed layout (0 where there are no edges)
@@ -625,50 +723,46 @@ void sum_terms(const std::vector<TermGw> &gw, double *glam, hipStream_t s) {
 // tape = 1: z and x' are two arrays that every iteration reuses, encoded behind their sweep (x' is still read by the next iteration's
 // first two steps, which is before its sweep rewrites it).
 void pd2_vjp(const double *y, const double *lambdas, const double *dims, const int *ns, int nds, int npen, int K, const double *g, double *x,
-             double *gy, double *glam, int tape, hipStream_t s) {
+             double *gy, double *glam, int tape, hipStream_t s, const double *norms) {
     const long n = total(ns, nds);
     const size_t bytes = sizeof(double) * (size_t)n;
     const int d0 = (int)(dims[0] - 1), d1 = npen >= 2 ? (int)(dims[1] - 1) : d0;
     const FibreGeom g0 = fibres_along(ns, nds, d0), g1 = fibres_along(ns, nds, d1);
-    Scratch kept(pd_vjp_tape_bytes(0, dims, ns, nds, npen, K, tape));
-    // tape = 1: the live outputs (one per term), then per k the words of z_k and of x'_k
-    const size_t w0 = (size_t)vjp_units(g0), w1 = npen >= 2 ? (size_t)vjp_units(g1) : 0;
-    unsigned *const words = tape ? reinterpret_cast<unsigned *>(kept.d() + (size_t)npen * (size_t)n) : nullptr;
+    std::vector<SweepTape> kept_of = pd_tapes(0, dims, norms, ns, nds, npen, K, tape);
+    Scratch kept(tape_bytes(kept_of));
+    tape_carve(kept_of, kept.d());
+    const SweepTape &t0 = kept_of[0], &t1 = kept_of[npen >= 2 ? 1 : 0];
     std::vector<TermGw> gw((size_t)npen);
-    term_gw(gw[0], g0, glam != nullptr);
-    if (npen >= 2) term_gw(gw[1], g1, glam != nullptr);
+    term_gw(gw[0], g0, glam != nullptr, t0.l2);
+    if (npen >= 2) term_gw(gw[1], g1, glam != nullptr, t1.l2);
     const long units = std::max(vjp_units(g0), vjp_units(g1));
     Scratch S(sizeof(Summary) * (size_t)units), R(sizeof(Resolved) * (size_t)units);
     if (npen == 1) {   // (x + p stays y: every iteration repeats the first)
-        tv1_fibres(y, kept.d(), ns, nds, d0, lambdas[0], nullptr, s);
-        if (tape) vjp_encode(kept.d(), words, g0, s);
-        if (x) PTV_HIP(hipMemcpyAsync(x, kept.d(), bytes, hipMemcpyDeviceToDevice, s));
-        vjp_launch_taped<VJP_PLAIN>(kept.d(), words, g, gy, gw[0].d(), g0, S.as<Summary>(), R.as<Resolved>(), VjpEpi{}, s);
+        tape_prox(y, t0, 0, ns, nds, d0, lambdas[0], nullptr, s);
+        if (t0.w(0)) vjp_encode(t0.y(0), t0.w(0), g0, s);
+        if (x) PTV_HIP(hipMemcpyAsync(x, t0.y(0), bytes, hipMemcpyDeviceToDevice, s));
+        tape_vjp<VJP_PLAIN>(t0, 0, g, gy, gw[0].d(), ns, nds, d0, lambdas[0], g0, S.as<Summary>(), R.as<Resolved>(), VjpEpi{}, s);
     } else {
         Scratch t(bytes), p(bytes), q(bytes);
-        auto zk = [&](int k) { return kept.d() + (tape ? 0 : (size_t)(2 * k) * (size_t)n); };
-        auto xk = [&](int k) { return kept.d() + (tape ? (size_t)n : (size_t)(2 * k + 1) * (size_t)n); };
-        auto cz = [&](int k) { return tape ? words + (size_t)k * (w0 + w1) : nullptr; };
-        auto cx = [&](int k) { return tape ? words + (size_t)k * (w0 + w1) + w0 : nullptr; };
+        auto zk = [&](int k) { return t0.y(k); };
+        auto xk = [&](int k) { return t1.y(k); };
         const double *xc = y;
         for (int k = 0; k < K; k++) {
             if (k == 0) {   // p = q = 0
-                tv1_fibres(y, zk(0), ns, nds, d0, lambdas[0], nullptr, s);
+                tape_prox(y, t0, 0, ns, nds, d0, lambdas[0], nullptr, s);
                 lincomb(p.d(), y, 1.0, zk(0), -1.0, nullptr, 0, nullptr, 0, n, s);
-                tv1_fibres(zk(0), xk(0), ns, nds, d1, lambdas[1], nullptr, s);
+                tape_prox(zk(0), t1, 0, ns, nds, d1, lambdas[1], nullptr, s);
                 lincomb(q.d(), zk(0), 1.0, xk(0), -1.0, nullptr, 0, nullptr, 0, n, s);
             } else {
                 lincomb(t.d(), xc, 1.0, p.d(), 1.0, nullptr, 0, nullptr, 0, n, s);
-                tv1_fibres(t.d(), zk(k), ns, nds, d0, lambdas[0], nullptr, s);
+                tape_prox(t.d(), t0, k, ns, nds, d0, lambdas[0], nullptr, s);
                 lincomb(p.d(), p.d(), 1.0, xc, 1.0, zk(k), -1.0, nullptr, 0, n, s);
                 lincomb(t.d(), zk(k), 1.0, q.d(), 1.0, nullptr, 0, nullptr, 0, n, s);
-                tv1_fibres(t.d(), xk(k), ns, nds, d1, lambdas[1], nullptr, s);
+                tape_prox(t.d(), t1, k, ns, nds, d1, lambdas[1], nullptr, s);
                 lincomb(q.d(), q.d(), 1.0, zk(k), 1.0, xk(k), -1.0, nullptr, 0, n, s);
             }
-            if (tape) {
-                vjp_encode(zk(k), cz(k), g0, s);
-                vjp_encode(xk(k), cx(k), g1, s);
-            }
+            if (t0.w(k)) vjp_encode(zk(k), t0.w(k), g0, s);
+            if (t1.w(k)) vjp_encode(xk(k), t1.w(k), g1, s);
             xc = xk(k);
         }
         if (x) PTV_HIP(hipMemcpyAsync(x, xc, bytes, hipMemcpyDeviceToDevice, s));
@@ -678,8 +772,8 @@ void pd2_vjp(const double *y, const double *lambdas, const double *dims, const i
             second.final = first.final = k == K - 1;
             second.add_gw = first.add_gw = k != K - 1;
             first.gU = gy;
-            vjp_launch_taped<VJP_PD2>(xk(k), cx(k), second.final ? g : D, D, gw[1].d(), g1, S.as<Summary>(), R.as<Resolved>(), second, s);
-            vjp_launch_taped<VJP_PD2>(zk(k), cz(k), D, D, gw[0].d(), g0, S.as<Summary>(), R.as<Resolved>(), first, s);
+            tape_vjp<VJP_PD2>(t1, k, second.final ? g : D, D, gw[1].d(), ns, nds, d1, lambdas[1], g1, S.as<Summary>(), R.as<Resolved>(), second, s);
+            tape_vjp<VJP_PD2>(t0, k, D, D, gw[0].d(), ns, nds, d0, lambdas[0], g0, S.as<Summary>(), R.as<Resolved>(), first, s);
         }
     }
     if (glam) sum_terms(gw, glam, s);
@@ -695,14 +789,14 @@ void pd2_vjp(const double *y, const double *lambdas, const double *dims, const i
 // tape = 1: the p_i of an iteration live in P arrays that every iteration reuses (the combine needs all of them), each encoded behind
 // its sweep.
 void pdp_vjp(const double *y, const double *lambdas, const double *dims, const int *ns, int nds, int P, int K, const double *g, double *x,
-             double *gy, double *glam, int tape, hipStream_t s) {
+             double *gy, double *glam, int tape, hipStream_t s, const double *norms) {
     const long n = total(ns, nds);
     const size_t bytes = sizeof(double) * (size_t)n;
-    Scratch kept(pd_vjp_tape_bytes(1, dims, ns, nds, P, K, tape));
-    auto pk = [&](int k, int i) { return kept.d() + ((tape ? 0 : (size_t)k * (size_t)P) + (size_t)i) * (size_t)n; };
-    std::vector<size_t> woff((size_t)P + 1, 0);   // tape = 1: where term i's words start inside an iteration's block
-    unsigned *const words = tape ? reinterpret_cast<unsigned *>(kept.d() + (size_t)P * (size_t)n) : nullptr;
-    auto ck = [&](int k, int i) { return tape ? words + (size_t)k * woff[(size_t)P] + woff[(size_t)i] : nullptr; };
+    std::vector<SweepTape> kept_of = pd_tapes(1, dims, norms, ns, nds, P, K, tape);
+    Scratch kept(tape_bytes(kept_of));
+    tape_carve(kept_of, kept.d());
+    auto pk = [&](int k, int i) { return kept_of[(size_t)i].y(k); };
+    auto ck = [&](int k, int i) { return kept_of[(size_t)i].w(k); };
     std::vector<std::unique_ptr<Scratch>> z;
     std::vector<FibreGeom> geo;
     std::vector<TermGw> gw((size_t)P);
@@ -710,9 +804,8 @@ void pdp_vjp(const double *y, const double *lambdas, const double *dims, const i
     for (int i = 0; i < P; i++) {
         z.emplace_back(new Scratch(bytes));
         geo.push_back(fibres_along(ns, nds, (int)(dims[i] - 1)));
-        term_gw(gw[(size_t)i], geo.back(), glam != nullptr);
+        term_gw(gw[(size_t)i], geo.back(), glam != nullptr, kept_of[(size_t)i].l2);
         units = std::max(units, vjp_units(geo.back()));
-        woff[(size_t)i + 1] = woff[(size_t)i] + (size_t)vjp_units(geo.back());
         PTV_HIP(hipMemcpyAsync(z.back()->d(), y, bytes, hipMemcpyDeviceToDevice, s));
     }
     Scratch xa(bytes), xb(bytes), partials(sizeof(double) * kReduceBlocks), acc(sizeof(double));
@@ -732,8 +825,8 @@ void pdp_vjp(const double *y, const double *lambdas, const double *dims, const i
     for (int k = 0; k < K; k++) {
         PtrPack pp{}, zp{};
         for (int i = 0; i < P; i++) {
-            tv1_fibres(z[(size_t)i]->d(), pk(k, i), ns, nds, (int)(dims[i] - 1), lambdas[i], nullptr, s);
-            if (tape) vjp_encode(pk(k, i), ck(k, i), geo[(size_t)i], s);
+            tape_prox(z[(size_t)i]->d(), kept_of[(size_t)i], k, ns, nds, (int)(dims[i] - 1), lambdas[i], nullptr, s);
+            if (ck(k, i)) vjp_encode(pk(k, i), ck(k, i), geo[(size_t)i], s);
             if (i < kMaxTerms) {
                 pp.v[i] = pk(k, i);
                 zp.v[i] = z[(size_t)i]->d();
@@ -758,7 +851,8 @@ void pdp_vjp(const double *y, const double *lambdas, const double *dims, const i
             e.gU = next;
             e.final = i == 0;
             e.add_gw = k != K - 1;
-            vjp_launch_taped<VJP_PD>(pk(k, i), ck(k, i), chi, z[(size_t)i]->d(), gw[(size_t)i].d(), geo[(size_t)i], S.as<Summary>(), R.as<Resolved>(), e, s);
+            tape_vjp<VJP_PD>(kept_of[(size_t)i], k, chi, z[(size_t)i]->d(), gw[(size_t)i].d(), ns, nds, (int)(dims[i] - 1), lambdas[i], geo[(size_t)i],
+                             S.as<Summary>(), R.as<Resolved>(), e, s);
         }
         chi = next;
     }
@@ -770,10 +864,10 @@ void pdp_vjp(const double *y, const double *lambdas, const double *dims, const i
 }  // namespace
 
 void pd_vjp(int which, const double *y, const double *lambdas, const double *dims, const int *ns, int nds, int npen, int iters, const double *g,
-            double *x, double *gy, double *glam, int tape, hipStream_t s) {
+            double *x, double *gy, double *glam, int tape, hipStream_t s, const double *norms) {
     if (total(ns, nds) == 0) return;
-    if (which == 0) pd2_vjp(y, lambdas, dims, ns, nds, npen, iters, g, x, gy, glam, tape, s);
-    else            pdp_vjp(y, lambdas, dims, ns, nds, npen, iters, g, x, gy, glam, tape, s);
+    if (which == 0) pd2_vjp(y, lambdas, dims, ns, nds, npen, iters, g, x, gy, glam, tape, s, norms);
+    else            pdp_vjp(y, lambdas, dims, ns, nds, npen, iters, g, x, gy, glam, tape, s, norms);
 }
 
 }  // namespace ptv

@@ -130,25 +130,65 @@ def tv1_2d_batch(xs, w, max_iters=0, out=None):
     return y, info
 
 
-def tvgen(x, ws, ds, max_iters=0, method=None, out=None):
+def _norms(ps, count, what="ps"):
+    """The norms of `count` terms as the C entry points take them (float64, each 1 or 2), or None for ps = None."""
+    if ps is None:
+        return None
+    norms = np.array(ps, dtype=np.float64).reshape(-1)
+    if norms.size != count:
+        raise ValueError(f"{what}: {norms.size} norms for {count} penalties")
+    if not np.all((norms == 1) | (norms == 2)):
+        raise NotImplementedError(f"{what}: only p = 1 (TV-L1) and p = 2 (TV-L2) are implemented on the device, got {list(norms)}")
+    return norms
+
+
+def tvp_2d(x, w_col, w_row, p_col, p_row, max_iters=0, out=None):
+    """Douglas-Rachford on an HBM-resident (M, N) image with the penalty ``w_col * ||diff||_{p_col}`` on every column and
+    ``w_row * ||diff||_{p_row}`` on every row, p in {1, 2} (proxtv_DR2_TVp_dev).  Returns (y, info)."""
+    _check(x, "x")
+    if x.dim() != 2:
+        raise ValueError(f"x: expected an (M, N) image, got {x.dim()} dimensions")
+    norms = _norms((p_col, p_row), 2, "p_col / p_row")
+    y = _out(out, x)
+    info = np.zeros(_N_INFO)
+    M, N = x.shape
+    with torch.cuda.device(x.device):
+        lib = _lib.require_device()
+        lib.proxtv_DR2_TVp_dev(M, N, x.data_ptr(), float(w_col), float(w_row), norms[0], norms[1], y.data_ptr(), int(max_iters),
+                               info.ctypes.data, _stream(x.device))
+    _lib.check("device.tvp_2d")
+    return y, info
+
+
+def tvgen(x, ws, ds, max_iters=0, method=None, out=None, ps=None):
     """N-D TV-L1 on an HBM-resident column-major array.  method: None = reference dispatch (2 terms -> 'pd2',
-    otherwise 'pd'); 'pdr' = parallel Douglas-Rachford; 'yang' = Yang ADMM (2-D / 3-D, one lambda per dim)."""
+    otherwise 'pd'); 'pdr' = parallel Douglas-Rachford; 'yang' = Yang ADMM (2-D / 3-D, one lambda per dim).
+    ps (one of {1, 2} per term, or None = all 1): the norm of every term's penalty, ``w * ||diff||_p`` per fibre
+    (proxtv_PD_TVp_dev; 'pd2', 'pd' and 'pdr')."""
     _check(x, "x")
     with torch.cuda.device(x.device):
-        return _tvgen(x, ws, ds, max_iters, method, _out(out, x))
+        return _tvgen(x, ws, ds, max_iters, method, _out(out, x), ps)
 
 
-def _tvgen(x, ws, ds, max_iters, method, y):
+def _tvgen(x, ws, ds, max_iters, method, y, ps=None):
     lib = _lib.require_device()
     info = np.zeros(_N_INFO)
     ns = np.array(x.shape, dtype=np.int32)
     lam = np.array(ws, dtype=np.float64)
     dims = np.array(ds, dtype=np.float64)
     npen = lam.size
+    norms = _norms(ps, npen)
     _stream = lambda: globals()["_stream"](x.device)   # noqa: E731
     if method is None:
         method = "pd2" if npen == 2 else "pd"
-    if method == "pd2":
+    if norms is not None:
+        if method not in ("pd2", "pd", "pdr"):
+            raise NotImplementedError(f"method {method!r} takes no norms (ps goes with 'pd2', 'pd' and 'pdr')")
+        which = {"pd2": 0, "pd": 1, "pdr": 2}[method]
+        scaled = lam * (1 if which == 0 else npen)
+        lib.proxtv_PD_TVp_dev(which, x.data_ptr(), scaled.ctypes.data, norms.ctypes.data, dims.ctypes.data, y.data_ptr(),
+                              info.ctypes.data, ns.ctypes.data, x.dim(), npen, int(max_iters), _stream())
+    elif method == "pd2":
         lib.proxtv_PD2_TV_dev(x.data_ptr(), lam.ctypes.data, dims.ctypes.data, y.data_ptr(), info.ctypes.data,
                               ns.ctypes.data, x.dim(), npen, int(max_iters), _stream())
     elif method in ("pd", "pdr"):
@@ -320,7 +360,8 @@ def _tape(tape):
     return 1 if tape == "steps" else 0
 
 
-def dr2_vjp(x, g, w_col, w_row=None, max_iters=0, weights_col=None, weights_row=None, need_gw=False, need_y=False, tape="outputs"):
+def dr2_vjp(x, g, w_col, w_row=None, max_iters=0, weights_col=None, weights_row=None, need_gw=False, need_y=False, tape="outputs",
+            p_col=1, p_row=1):
     """The derivative of the Douglas-Rachford solves ``tv1_2d(x, w_col, w_row=w_row)`` / ``tv1w_2d(x, weights_col, weights_row)`` /
     ``tv1_2d_batch`` applied to the cotangent `g` of their result: returns (gx, gw_col, gw_row, glam, y).
 
@@ -330,9 +371,18 @@ def dr2_vjp(x, g, w_col, w_row=None, max_iters=0, weights_col=None, weights_row=
     alone.  y (`need_y`) is the forward result of the call's own, unfused recurrence: device.tv1_2d's up to rounding.  One call:
     proxtv_DR2_TV_vjp_tape_dev (include/proxtv_amd.h), which keeps 2 (max_iters + 1) arrays of x's size in pool scratch while it runs
     -- or, with ``tape="steps"``, the step codes of those arrays (1/32 of the bytes) and two arrays of x's size; every result is the same
-    bits.  A `g` in another layout is copied."""
+    bits.  A `g` in another layout is copied.
+
+    p_col / p_row in {1, 2}: the derivative of ``tvp_2d(x, w_col, w_row, p_col, p_row)`` (proxtv_DR2_TVp_vjp_dev) -- one (M, N) image,
+    uniform penalties only.  A TV-L2 direction has no per-edge gradient: gw_col / gw_row come back None and glam (`need_gw`) holds the
+    gradients in (w_col, w_row).  Its sweeps keep their float64 output and one multiplier per fibre under either tape."""
     _check(x, "x")
     tape = _tape(tape)
+    norms = _norms((p_col, p_row), 2, "p_col / p_row")
+    if np.any(norms == 2):
+        if weights_col is not None or weights_row is not None:
+            raise ValueError("per-edge weight maps go with p = 1 only: TV-L2 has one penalty per fibre")
+        return _dr2p_vjp(x, g, w_col, w_col if w_row is None else w_row, norms, max_iters, need_gw, need_y, tape)
     if x.dim() not in (2, 3):
         raise ValueError(f"x: expected an (M, N) image or an (M, N, B) batch, got {x.dim()} dimensions")
     if not (isinstance(g, torch.Tensor) and g.is_cuda and g.dtype == torch.float64):
@@ -375,7 +425,34 @@ def dr2_vjp(x, g, w_col, w_row=None, max_iters=0, weights_col=None, weights_row=
     return gx, gw_col, gw_row, glam, y
 
 
-def tvgen_vjp(x, g, ws, ds, iters, method=None, need_glam=False, need_y=False, tape="outputs"):
+def _cotangent(g, x):
+    if not (isinstance(g, torch.Tensor) and g.is_cuda and g.dtype == torch.float64):
+        raise ValueError("g: expected a float64 CUDA tensor")
+    if g.device != x.device:
+        raise ValueError(f"g: lives on {g.device}, the input on {x.device}")
+    if tuple(g.shape) != tuple(x.shape):
+        raise ValueError(f"g: shape {tuple(g.shape)}, expected {tuple(x.shape)}")
+    return g if _is_colmajor(g) else to_colmajor(g)
+
+
+def _dr2p_vjp(x, g, w_col, w_row, norms, max_iters, need_gw, need_y, tape):
+    if x.dim() != 2:
+        raise ValueError(f"x: a TV-L2 direction takes one (M, N) image, got {x.dim()} dimensions")
+    g = _cotangent(g, x)
+    M, N = x.shape
+    gx = colmajor_empty(x.shape, device=x.device)
+    y = colmajor_empty(x.shape, device=x.device) if need_y else None
+    glam = np.zeros(2) if need_gw else None
+    ptr = lambda t: t.data_ptr() if t is not None and t.numel() else 0   # noqa: E731
+    with torch.cuda.device(x.device):
+        lib = _lib.require_device()
+        lib.proxtv_DR2_TVp_vjp_dev(M, N, ptr(x), float(w_col), float(w_row), norms[0], norms[1], ptr(g), ptr(y), ptr(gx),
+                                   glam.ctypes.data if need_gw else 0, int(max_iters), tape, _stream(x.device))
+    _lib.check("device.dr2_vjp")
+    return gx, None, None, glam, y
+
+
+def tvgen_vjp(x, g, ws, ds, iters, method=None, need_glam=False, need_y=False, tape="outputs", ps=None):
     """The derivative of ``tvgen(x, ws, ds, method=method)`` applied to the cotangent `g` of its result: returns (gx, glam, y).
 
     `iters` is the iteration count the forward solve reported (``info[0]``): the call runs exactly that many iterations of its own,
@@ -385,7 +462,10 @@ def tvgen_vjp(x, g, ws, ds, iters, method=None, need_glam=False, need_y=False, t
     works with ws * len(ws); the chain rule through that scaling is applied here).  y (`need_y`) is the forward result of the call's own
     recurrence: tvgen's up to rounding.  One call: proxtv_PD_TV_vjp_tape_dev (include/proxtv_amd.h), which keeps len(ws) * iters ('pd') or
     2 * iters ('pd2') arrays of x's size in pool scratch while it runs -- or, with ``tape="steps"``, their step codes (1/32 of the bytes)
-    and one array of x's size per term; every result is the same bits.  A `g` in another layout is copied."""
+    and one array of x's size per term; every result is the same bits.  A `g` in another layout is copied.
+
+    ps (one of {1, 2} per term, or None = all 1): the derivative of ``tvgen(x, ws, ds, method=method, ps=ps)``
+    (proxtv_PD_TVp_vjp_dev); a TV-L2 term's sweeps keep their float64 output and one multiplier per fibre under either tape."""
     _check(x, "x")
     tape = _tape(tape)
     if not (isinstance(g, torch.Tensor) and g.is_cuda and g.dtype == torch.float64):
@@ -401,6 +481,7 @@ def tvgen_vjp(x, g, ws, ds, iters, method=None, need_glam=False, need_y=False, t
     npen = lam.size
     if dims.size != npen:
         raise ValueError(f"ds: {dims.size} dimensions for {npen} penalties")
+    norms = _norms(ps, npen)
     if method is None:
         method = "pd2" if npen == 2 else "pd"
     if method not in ("pd2", "pd"):
@@ -414,9 +495,14 @@ def tvgen_vjp(x, g, ws, ds, iters, method=None, need_glam=False, need_y=False, t
     ptr = lambda t: t.data_ptr() if t is not None and t.numel() else 0   # noqa: E731
     with torch.cuda.device(x.device):
         lib = _lib.require_device()
-        lib.proxtv_PD_TV_vjp_tape_dev(0 if method == "pd2" else 1, ptr(x), scaled.ctypes.data, dims.ctypes.data, ns.ctypes.data, x.dim(),
-                                      npen, int(iters), ptr(g), ptr(y), ptr(gx), glam.ctypes.data if need_glam else 0, tape,
-                                      _stream(x.device))
+        if norms is None:
+            lib.proxtv_PD_TV_vjp_tape_dev(0 if method == "pd2" else 1, ptr(x), scaled.ctypes.data, dims.ctypes.data, ns.ctypes.data, x.dim(),
+                                          npen, int(iters), ptr(g), ptr(y), ptr(gx), glam.ctypes.data if need_glam else 0, tape,
+                                          _stream(x.device))
+        else:
+            lib.proxtv_PD_TVp_vjp_dev(0 if method == "pd2" else 1, ptr(x), scaled.ctypes.data, norms.ctypes.data, dims.ctypes.data,
+                                      ns.ctypes.data, x.dim(), npen, int(iters), ptr(g), ptr(y), ptr(gx),
+                                      glam.ctypes.data if need_glam else 0, tape, _stream(x.device))
     _lib.check("device.tvgen_vjp")
     if glam is not None:
         glam *= scale
