@@ -18,7 +18,8 @@
  * the reference's cffi cdef declares (prox_tv/prox_tv_build.py:13-76) is exported, so that cdef links against this
  * library unmodified: the alternative 1-D TV-L1 algorithms (projected Newton, Kolmogorov's and Johnson's solvers,
  * Condat's taut string) are entry points of the one exact solver -- the minimiser is unique -- and the general-p
- * TV-Lp schemes report RC_ERROR for p outside {1, 2} (DESIGN.md "Out of scope").
+ * TV-Lp schemes report RC_ERROR for p outside {1, 2} unless option general_p is set (below: then 1.002 < p < 100 is
+ * served by the general-p fibre prox, proxtv_tvpg_fibres_dev).
  */
 #ifndef PROXTV_AMD_H
 #define PROXTV_AMD_H
@@ -194,6 +195,14 @@ void proxtv_release_scratch(void);
                       its first piece from its own first row: the hole of DESIGN.md 6 (ii')) so that the suite can watch the certifier catch
                       it -- RESULTS MAY BE WRONG while it is non-zero (a warning is printed) */
 int proxtv_set_option(const char *key, int value);
+/* One more key of proxtv_set_option, a feature switch rather than a tuning knob (environment: PROXTV_GENERAL_P):
+     general_p      0 (default): every entry point refuses a norm p outside {1, 2} -- RC_ERROR, as it always has ;
+                    1: TV, GP_TVp / OGP_TVp / FISTA_TVp / FW_TVp / GPFW_TVp, DR2_TV, PD2_TV, PD_TV and their device forms
+                    proxtv_tvp_fibres_dev, proxtv_DR2_TVp_dev, proxtv_PD_TVp_dev (which = 0, 1) take 1.002 < p < 100 (the reference's own
+                    LPPROJ_PSMALL / LPPROJ_PLARGE) and serve it with the general-p fibre prox below.  The 1-D host symbols then fill
+                    info[0] = outer iterations, info[1] = the achieved duality gap, info[2] = RC_OK, or RC_ITERS where the iteration cap
+                    was hit.  PDR_TV, the Yang solvers and every *_vjp entry point refuse such a norm whatever the option; p = inf and
+                    p >= 100 stay refused.  With 0 every entry point's results are what they were without the key, bit for bit. */
 
 /* Device-pointer solvers: every double* is an HBM pointer valid on the current device, `stream` is
    a hipStream_t (NULL = the library's per-thread stream), `info` is a HOST double[3] or NULL.
@@ -354,6 +363,23 @@ int proxtv_tvp_fibres_dev(const double *in, double *out, const int *ns, int nds,
 int proxtv_DR2_TVp_dev(size_t M, size_t N, const double *unary, double W1, double W2, double norm1, double norm2,
                        double *s, int maxit, double *info, void *stream);
 
+/* The TV-Lp fibre prox for general p, always available (no option): out = argmin 1/2 ||x - in||^2 + lambda ||Dx||_p along `dim` of every
+   fibre, 1.002 < p < 100.  p = 1 and p = 2 go to the exact solvers above and return their bits (gap is then 0); any other p: returns 0 with
+   proxtv_last_error set.  Per fibre, with q = p / (p - 1): n == 1 or lambda <= 0 -- a copy; T^-1 D in inside the ball ||u||_q <= lambda --
+   the mean; otherwise the dual min 1/2 ||D'u - in||^2 over that ball is solved by nested Newton iterations on its KKT system (every step
+   one tridiagonal LDL' sweep) and out = in - D'u, which keeps the fibre's mean.  The iteration stops on the fibre's own
+   duality gap, lambda ||D out||_p - u'D out, at max(1e-8, 4e-13 * 1/2 ||in - mean||^2) -- the reference's solvers stop at 1e-5 -- and
+   a hard cap of 1500 forward sweeps bounds every fibre's work: a fibre that gets there keeps its best feasible iterate and is counted.
+     gap         DEVICE double per fibre, or NULL: the achieved gap, laid out as mu of proxtv_tv2_fibres_dev; 0 for the closed forms
+   Counters (proxtv_debug_counter): "tvp_fibres", fibres solved iteratively; "tvp_capped", fibres the cap stopped above their target.
+   One lane per fibre: a single long fibre runs on one lane (DESIGN.md 6h gives the bound).  Scratch comes from the pool -- four arrays of
+   the data's size, six along dimension 0, 12 bytes per fibre; beyond the pool's cap (PROXTV_POOL_CAP_MB) the call is refused and
+   proxtv_last_error names the bytes.  out may overlap in (the solve then goes through scratch); gap may overlap neither.  No atomics, no
+   warm start across fibres: a fibre's result depends on that fibre alone and the same call gives the same bits.  Synchronises the stream;
+   returns 1, or 0 with proxtv_last_error set. */
+int proxtv_tvpg_fibres_dev(const double *in, double *out, double *gap /*or NULL*/, const int *ns /*host*/, int nds, int dim, double lambda,
+                           double p, void *stream);
+
 /* The TV-L2 fibre prox on its own, with its multiplier: out = argmin 1/2 ||x - in||^2 + lambda ||Dx||_2 along `dim` of every fibre --
    the bits of proxtv_tvp_fibres_dev(p = 2).  Per fibre of n samples, D the (n-1) x n difference matrix and T = D D' = tridiag(-1, 2, -1):
    out = in - D'u, where either u = T^-1 D in lies inside the ball ||u|| <= lambda (out is then the mean of in), or (T + mu I) u = D in
@@ -434,7 +460,8 @@ int    proxtv_debug_why(unsigned *dst);
    "repair_launches" (sweep_repair_kernel behind them), "repair_jobs_launches" (option repair_jobs), "pin_sweeps" (sweeps the
    pinning solver took), "pin_cap_next_rung" (sweeps its grid-wide variant handed on after the level cap), "tv2_long_fibres"
    (TV-L2 fibres solved parallel inside the fibre), "optimistic_solves" / "optimistic_redone" (option optimistic), "certify_sweeps" / "certify_failures" / "certify_skipped" (option certify:
-   sweeps checked, fibres that failed and were re-solved, sweeps that could not be checked).  -1 for an unknown name. */
+   sweeps checked, fibres that failed and were re-solved, sweeps that could not be checked), "tvp_fibres" / "tvp_capped" (general-p fibres
+   solved iteratively, and those an iteration cap stopped).  -1 for an unknown name. */
 long   proxtv_debug_counter(const char *name);
 /* Geometry policy the adaptive chunk kernel currently uses on this thread (the highest over the sweep families):
    0 = 16-sample warm-up zones (noisy data, small lambda), 1 = the same, robust instantiation (walks may run past

@@ -17,7 +17,11 @@ TV-L2 (p = 2) is covered as well: ``tv2_1d``, ``tvp_1d(p=2)``, ``tvp_2d`` and ``
 is solved EXACTLY on the device (trust-region / More-Sorensen on the tridiagonal dual), which the reference's own p = 2
 solver is not (it stops at a duality gap of 1e-5 and warm-starts fibres from each other: its results depend on the
 thread count); results agree with the reference within the reference's own guarantee, see DESIGN.md.
-Out of scope (raise ``NotImplementedError``): general p (``tvp_1d`` / ``tvp_2d`` / ``tvgen`` with p not in {1, 2}).
+General p (1.002 < p < 100, the reference's own range) is opt-in: after ``proxtv_amd.general_p(True)`` (or with PROXTV_GENERAL_P=1 in
+the environment) ``tvp_1d`` / ``tvp_2d`` / ``tvgen`` take such a p, and every fibre prox of that norm is solved on the device by nested
+Newton iterations on the dual's KKT system to a duality gap of 1e-8 (the reference stops at 1e-5).  While the switch is off
+-- the default -- a p outside {1, 2} raises ``NotImplementedError`` as it always has, and nothing else changes.
+:func:`proxtv_amd.device.tvp_fibres` is that fibre prox on HBM-resident arrays, always available.  p = inf and p >= 100 are not implemented.
 ``tv1_1d``'s alternative method names are served by the one exact HIP solver.
 
 Reproducibility: by default the same call returns the same bits whatever ran before -- which kernel geometry a sweep takes is a
@@ -30,7 +34,7 @@ import numpy as np
 from . import _lib
 from ._lib import ProxTVError  # noqa: F401
 
-__all__ = ["tv1_1d", "tv1w_1d", "tv2_1d", "tvp_1d", "tv1_2d", "tv1w_2d", "tvp_2d", "tvgen", "tv1_2d_batch",
+__all__ = ["general_p", "tv1_1d", "tv1w_1d", "tv2_1d", "tvp_1d", "tv1_2d", "tv1w_2d", "tvp_2d", "tvgen", "tv1_2d_batch",
            "force_float_scalar", "force_float_matrix", "ProxTVError"]
 
 # The maximum number of returned info parameters (reference: prox_tv/__init__.py:67).
@@ -59,6 +63,12 @@ def force_float_matrix(x):
     if x.dtype != np.dtype("float64"):
         return x.astype("float")
     return x
+
+
+def general_p(on):
+    """Switch the general-p norms (1.002 < p < 100, p != 2) of tvp_1d / tvp_2d / tvgen and of the C entry points behind them on or off
+    (proxtv_set_option("general_p", ...); process-wide, off by default).  Returns the previous setting."""
+    return bool(_lib.load().proxtv_set_option(b"general_p", 1 if on else 0))
 
 
 def _contig(x):
@@ -152,13 +162,13 @@ def tv2_1d(x, w, method="mspg"):
 
 
 def tvp_1d(x, w, p, method="gpfw", max_iters=0):
-    """1D proximal operator for the l_p norm (reference: prox_tv/__init__.py:311-352): p = 1 and p = 2 are implemented
-    (the exact TV-L1 / TV-L2 device solvers, whatever `method`); general p is out of scope."""
+    """1D proximal operator for the l_p norm (reference: prox_tv/__init__.py:311-352): p = 1 and p = 2 are the exact TV-L1 / TV-L2
+    device solvers, whatever `method`; with general_p(True) any 1.002 < p < 100 is the one general-p device solver (all three
+    methods), stopped at a duality gap of 1e-8."""
     assert method in ("gp", "fw", "gpfw")
     assert w >= 0
     assert p >= 1
-    if p not in (1, 2):
-        raise NotImplementedError("proxtv_amd implements p = 1 and p = 2 only (general-p TV is out of scope)")
+    _lib.check_forward_norms((p,))
     w = force_float_scalar(w)
     x = _contig(force_float_matrix(x))
     info = np.zeros(_N_INFO)
@@ -229,13 +239,12 @@ def tv1w_2d(x, w_col, w_row, max_iters=0, n_threads=1):
 
 def tvp_2d(x, w_col, w_row, p_col, p_row, n_threads=1, max_iters=0):
     r"""2D proximal operator for :math:`\ell_p` norms (reference: prox_tv/__init__.py:484-530): DR2_TV with separate
-    column / row penalties and norms; p in {1, 2} is implemented."""
+    column / row penalties and norms; p in {1, 2}, and with general_p(True) any 1.002 < p < 100."""
     assert w_col >= 0
     assert w_row >= 0
     assert p_col >= 1
     assert p_row >= 1
-    if p_col not in (1, 2) or p_row not in (1, 2):
-        raise NotImplementedError("proxtv_amd implements p = 1 and p = 2 only (general-p TV is out of scope)")
+    _lib.check_forward_norms((p_col, p_row))
     info = np.zeros(_N_INFO)
     x = np.asfortranarray(x, dtype="float64")
     w_col = force_float_scalar(w_col)
@@ -269,8 +278,7 @@ def tvgen(x, ws, ds, ps, n_threads=1, max_iters=0):
     ws = force_float_matrix(ws)
     ps = force_float_matrix(ps)
     y = np.zeros(np.shape(x), order="F")
-    if np.any((ps != 1) & (ps != 2)):
-        raise NotImplementedError("proxtv_amd implements p = 1 and p = 2 only (general-p TV is out of scope)")
+    _lib.check_forward_norms(ps.ravel())      # (p in {1, 2}; with general_p(True) any 1.002 < p < 100)
     if not (ps.flags.c_contiguous or ps.flags.f_contiguous):
         ps = np.ascontiguousarray(ps)
     dims = np.array(ds, dtype=np.float64)            # cffi turns the `ds` sequence into a temporary double[]

@@ -88,6 +88,7 @@ SIGNATURES = {
                                           C.c_int, _dp, C.c_void_p]),
     "proxtv_DR2_TV_batch": (C.c_int, [C.c_size_t, C.c_size_t, C.c_size_t, _dp, C.c_double, C.c_double, _dp, C.c_int, _dp]),
     "proxtv_tvp_fibres_dev": (C.c_int, [_dp, _dp, _ip, C.c_int, C.c_int, C.c_double, C.c_double, C.c_void_p]),
+    "proxtv_tvpg_fibres_dev": (C.c_int, [_dp, _dp, _dp, _ip, C.c_int, C.c_int, C.c_double, C.c_double, C.c_void_p]),
     "proxtv_tv2_fibres_dev": (C.c_int, [_dp, _dp, _dp, _ip, C.c_int, C.c_int, C.c_double, C.c_void_p]),
     "proxtv_tv2_fibres_vjp_dev": (C.c_int, [_dp, _dp, _dp, _dp, _dp, _ip, C.c_int, C.c_int, C.c_double, C.c_void_p]),
     "proxtv_DR2_TVp_dev": (C.c_int, [C.c_size_t, C.c_size_t, _dp, C.c_double, C.c_double, C.c_double, C.c_double, _dp, C.c_int,
@@ -164,6 +165,31 @@ def load(build_if_missing=True):
         fn.restype, fn.argtypes = res, args
     _lib = lib
     return lib
+
+
+def option_value(key):
+    """The current value of a proxtv_set_option key (read by setting and restoring it: not for use while another thread sets options)."""
+    lib = load()
+    value = lib.proxtv_set_option(key.encode(), 0)
+    lib.proxtv_set_option(key.encode(), value)
+    return value
+
+
+P_GENERAL_MIN, P_GENERAL_MAX = 1.002, 100.0      # csrc/tvp.hpp: the range of the general-p solver (the reference's LPPROJ_PSMALL / _PLARGE)
+_ONLY_P12 = "proxtv_amd implements p = 1 and p = 2 only (general-p TV is out of scope)"
+
+
+def check_forward_norms(ps):
+    """The norms a forward solve takes: 1 and 2 always; with option general_p (proxtv_amd.general_p) any 1.002 < p < 100.  Raises the
+    NotImplementedError the package has always raised for the others."""
+    others = [float(p) for p in ps if p not in (1, 2)]
+    if not others:
+        return
+    if not option_value("general_p"):
+        raise NotImplementedError(_ONLY_P12)
+    bad = [p for p in others if not P_GENERAL_MIN < p < P_GENERAL_MAX]
+    if bad:
+        raise NotImplementedError(f"the general-p solver takes {P_GENERAL_MIN} < p < {P_GENERAL_MAX}, got {bad}")
 
 
 def last_error():

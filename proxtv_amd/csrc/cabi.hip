@@ -13,6 +13,7 @@
 #include "pointwise.hpp"
 #include "sweep.hpp"
 #include "tv2.hpp"
+#include "tvp.hpp"
 
 using namespace ptv;
 
@@ -134,13 +135,41 @@ void prox1d_host(const double *y, const double *w, double lam, double *x, int n,
     scope.finish();
 }
 
-bool check_norms(const double *norms, int npen) {   // returns whether any term is TV-L2
-    bool l2 = false;
+constexpr const char *kOnlyP12 = "only the p = 1 (TV-L1) and p = 2 (TV-L2) norms are implemented on the HIP path";
+
+// Whether a norm outside {1, 2} goes to the general-p solver: only with option general_p, and only inside the solver's range.
+// Throws what the entry point reports otherwise -- with the option off, the refusal every such norm has always got.
+bool general_norm(double p) {
+    if (p == 1 || p == 2) return false;
+    if (!options().general_p) reject(kOnlyP12);
+    if (!tvp_general_norm(p)) reject("option general_p: the general-p solver takes 1.002 < p < 100; other norms are not implemented on the HIP path");
+    return true;
+}
+
+// returns whether any term is not TV-L1 (TV-L2, or with `general` a general p: the loops then run their unfused forms)
+bool check_norms(const double *norms, int npen, bool general = false) {
+    bool other = false;
     for (int i = 0; i < npen; i++) {
-        if (norms[i] != 1 && norms[i] != 2) reject("only the p = 1 (TV-L1) and p = 2 (TV-L2) norms are implemented on the HIP path");
-        l2 = l2 || norms[i] == 2;
+        if (norms[i] != 1 && norms[i] != 2 && !(general && general_norm(norms[i]))) reject(kOnlyP12);
+        other = other || norms[i] != 1;
     }
-    return l2;
+    return other;
+}
+
+// the general-p prox of one host signal: info as the reference's TV-Lp solvers fill it (iterations, gap, RC_OK / RC_ITERS)
+void tvp1d_host(const double *y, double lam, double *x, int n, double p, double *info) {
+    TvpStats st;
+    if (n > 0) {
+        hipStream_t s = thread_stream();
+        SolveScope scope(s);
+        Staged in(y, (size_t)n, s);
+        Scratch out(sizeof(double) * (size_t)n);
+        const int ns[1] = {n};
+        st = tvp_fibres(in.d(), out.d(), nullptr, ns, 1, 0, lam, p, s);
+        download(x, out.d(), (size_t)n, s);
+        scope.finish();
+    }
+    if (info) { info[INFO_ITERS] = st.iters; info[INFO_GAP] = st.gap; info[INFO_RC] = st.capped ? RC_ITERS : RC_OK; }
 }
 
 long total(const int *ns, int nds) {
@@ -169,7 +198,7 @@ int TV(double *y, double lambda, double *x, double *info, int n, double p, Works
         return 0;
     }
     return guarded("TVopt", info, 1, [&] {
-        if (p != 1 && p != 2) reject("only the p = 1 (TV-L1) and p = 2 (TV-L2) norms are implemented on the HIP path");
+        if (general_norm(p)) { tvp1d_host(y, lambda, x, n, p, info); return; }
         prox1d_host(y, nullptr, lambda, x, n, 0.0, p);
         if (info) { info[INFO_RC] = RC_OK; info[INFO_ITERS] = 0; info[INFO_GAP] = 0; }
     });
@@ -274,11 +303,11 @@ void dp(int n, double *y, double lam, double *beta) {
 }
 
 // TV-Lp for general p (src/TVLPopt.cpp: GP_TVp :37, OGP_TVp :295, FISTA_TVp :583, FW_TVp :871, GPFW_TVp :1111): five
-// first-order schemes for min 1/2 ||x-y||^2 + lambda ||Dx||_p.  Out of scope for general p (SURVEY section 2 allows the
-// RC_ERROR stub); p = 1 and p = 2 have exact device solvers and are served by them, like TV().
+// first-order schemes for min 1/2 ||x-y||^2 + lambda ||Dx||_p.  p = 1 and p = 2 have exact device solvers and are served by them, like
+// TV(); a general p is refused (RC_ERROR) unless option general_p is set, and then all five are the one device solver of tvp.hip.
 static int tvp_host(const char *who, double *y, double lambda, double *x, double *info, int n, double p) {
     return guarded(who, info, 1, [&] {
-        if (p != 1 && p != 2) reject("only the p = 1 (TV-L1) and p = 2 (TV-L2) norms are implemented on the HIP path");
+        if (general_norm(p)) { tvp1d_host(y, lambda, x, n, p, info); return; }
         prox1d_host(y, nullptr, lambda, x, n, 0.0, p);
         if (info) { info[INFO_ITERS] = 0; info[INFO_GAP] = 0; info[INFO_RC] = RC_OK; }
     });
@@ -294,7 +323,7 @@ int DR2_TV(size_t M, size_t N, double *unary, double W1, double W2, double norm1
     // returns 0 on success like the reference (src/TV2Dopt.cpp:440); failures also return 0 with info[RC]=RC_ERROR
     return guarded("DR2_TV", info, 0, [&] {
         const double nrm[2] = {norm1, norm2};
-        const bool l2 = check_norms(nrm, 2);
+        const bool l2 = check_norms(nrm, 2, true);
         hipStream_t st = thread_stream();
         SolveScope scope(st);
         Staged u(unary, M * N, st);
@@ -326,7 +355,7 @@ int PD2_TV(double *y, double *lambdas, double *norms, double *dims, double *x, d
     return guarded("PD2_TV", info, 1, [&] {
         if (npen > 2) reject("this algorithm can not work with more than 2 penalties");   // src/TV2Dopt.cpp:95-96
         if (npen < 1) reject("at least one penalty term is required");
-        check_norms(norms, npen);
+        check_norms(norms, npen, true);
         check_dims(dims, npen, nds);
         hipStream_t st = thread_stream();
         SolveScope scope(st);
@@ -344,7 +373,7 @@ static int pd_family_host(const char *who, bool dr_variant, double *y, double *l
                           double *x, double *info, int *ns, int nds, int npen, int maxIters) {
     return guarded(who, info, 1, [&] {
         if (npen < 1) reject("at least one penalty term is required");
-        check_norms(norms, npen);
+        check_norms(norms, npen, !dr_variant);   // (a general p: PD_TV alone)
         check_dims(dims, npen, nds);
         for (int i = 0; i < npen; i++) lambdas[i] *= npen;   // caller memory, like src/TVNDopt.cpp:100-101 / :334-335
         hipStream_t st = thread_stream();
@@ -846,7 +875,7 @@ int proxtv_tvp_fibres_dev(const double *in, double *out, const int *ns, int nds,
                           void *stream) {
     return guarded("proxtv_tvp_fibres_dev", nullptr, 1, [&] {
         if (dim < 0 || dim >= nds) reject("dimension out of range");
-        if (p != 1 && p != 2) reject("only the p = 1 (TV-L1) and p = 2 (TV-L2) norms are implemented on the HIP path");
+        general_norm(p);   // (throws the refusal)
         hipStream_t st = pick(stream);
         SolveScope scope(st);
         const size_t n = (size_t)total(ns, nds);
@@ -860,6 +889,30 @@ int proxtv_tvp_fibres_dev(const double *in, double *out, const int *ns, int nds,
 
 // whether [a, a + na) and [b, b + nb) (counted in doubles) share a byte
 static bool spans_overlap(const double *a, size_t na, const double *b, size_t nb) { return a && b && na && nb && a < b + nb && b < a + na; }
+
+int proxtv_tvpg_fibres_dev(const double *in, double *out, double *gap, const int *ns, int nds, int dim, double lambda, double p, void *stream) {
+    return guarded("proxtv_tvpg_fibres_dev", nullptr, 1, [&] {
+        if (dim < 0 || dim >= nds) reject("dimension out of range");
+        if (p != 1 && p != 2 && !tvp_general_norm(p)) reject("the general-p solver takes 1.002 < p < 100; other norms are not implemented on the HIP path");
+        const size_t n = (size_t)total(ns, nds);
+        if (n == 0) return;
+        if (!in || !out) reject("in and out are required");
+        const size_t nf = n / (size_t)ns[dim];
+        if (spans_overlap(gap, nf, in, n) || spans_overlap(gap, nf, out, n)) reject("gap overlaps in or out");
+        hipStream_t st = pick(stream);
+        SolveScope scope(st);
+        OutGuard guard(out, n, {{in, n}});
+        if (p == 1 || p == 2) {   // the exact solvers' bits
+            prox_fibres(in, guard.ptr(), ns, nds, dim, lambda, p, st);
+            if (gap) PTV_HIP(hipMemsetAsync(gap, 0, sizeof(double) * nf, st));
+        } else {
+            tvp_fibres(in, guard.ptr(), gap, ns, nds, dim, lambda, p, st);
+        }
+        guard.commit(st);
+        PTV_HIP(hipStreamSynchronize(st));
+        scope.finish();
+    });
+}
 
 int proxtv_tv2_fibres_dev(const double *in, double *out, double *mu, const int *ns, int nds, int dim, double lambda, void *stream) {
     return guarded("proxtv_tv2_fibres_dev", nullptr, 1, [&] {
@@ -911,7 +964,7 @@ int proxtv_DR2_TVp_dev(size_t M, size_t N, const double *unary, double W1, doubl
                        int maxit, double *info, void *stream) {
     return guarded("proxtv_DR2_TVp_dev", info, 0, [&] {
         const double nrm[2] = {norm1, norm2};
-        const bool l2 = check_norms(nrm, 2);
+        const bool l2 = check_norms(nrm, 2, true);
         hipStream_t st = pick(stream);
         SolveScope scope(st);
         OutGuard out(s, M * N, {{unary, M * N}});
@@ -929,7 +982,7 @@ int proxtv_PD_TVp_dev(int which, const double *y, const double *lambdas_scaled, 
     return guarded("proxtv_PD_TVp_dev", info, 1, [&] {
         if (npen < 1) reject("at least one penalty term is required");
         if (which == 0 && npen > 2) reject("PD2 works with 1 or 2 penalties");
-        check_norms(norms, npen);
+        check_norms(norms, npen, which == 0 || which == 1);   // (a general p: the two Dykstra loops, not PDR)
         check_dims(dims, npen, nds);
         hipStream_t st = pick(stream);
         SolveScope scope(st);

@@ -46,6 +46,7 @@ constexpr OptionEntry kOptionTable[] = {
     {"profile", &Options::profile},
     {"why", &Options::why},
     {"trace", &Options::trace},
+    {"general_p", &Options::general_p},
     {"ablate", &Options::ablate},
     {"debug_legacy_rebuild", &Options::debug_legacy_rebuild},
 };
@@ -81,7 +82,7 @@ namespace {
 std::atomic<long> g_counters[CNT_COUNT];
 constexpr const char *kCounterNames[CNT_COUNT] = {"sweep_launches", "repair_launches", "repair_jobs_launches", "pin_sweeps",
                                                   "pin_cap_next_rung", "tv2_long_fibres", "optimistic_solves", "optimistic_redone", "certify_sweeps", "certify_failures",
-                                                  "certify_skipped", "reprobes"};
+                                                  "certify_skipped", "reprobes", "tvp_fibres", "tvp_capped"};
 }  // namespace
 void count_event(Counter c, long n) { g_counters[c].fetch_add(n, std::memory_order_relaxed); }
 long counter_value(const char *name) {
@@ -134,6 +135,7 @@ static void probe_device(int dev) {
         warm_pinlong();
         warm_pointwise();
         warm_tv2();
+        warm_tvp();
     } catch (const HipFailure &) {
         (void)hipGetLastError();   // not fatal: the first launch will load (or report) what this could not
         set_error("%s", before.c_str());   // ... and PTV_HIP recorded a message before it threw: a solve that then succeeds must not report it

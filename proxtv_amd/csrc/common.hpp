@@ -68,6 +68,8 @@ struct Options {
     int why = 0;        // tuning aid: count what marks sweeps dirty (proxtv_debug_why)
     int trace = 0;      // profiling aid: per-workgroup phase timestamps of the chunk kernel (proxtv_debug_trace)
     int ablate = 0;     // profiling aid, see ChunkPlan::ablate (results are WRONG when non-zero)
+    int general_p = 0;        // 1: the reference's entry points take a general norm (1.002 < p < 100) and serve it with tvp.hip; 0 (default): they
+                              // refuse every p outside {1, 2}, as they always have (proxtv_tvpg_fibres_dev takes it either way)
     int debug_legacy_rebuild = 0;   // test aid: the along-fibre kernel's rebuild with the semantics of rounds 1-4 (an unproven chunk values its first
                                     // piece from its own first row) -- results MAY BE WRONG; exists so that the suite can watch `certify` catch it
 };
@@ -88,6 +90,8 @@ enum Counter {
     CNT_CERTIFY_FAILURES,      // ... fibres that failed the check and were re-solved by the sequential walk
     CNT_CERTIFY_SKIPPED,       // ... sweeps that could not be checked (an output aliases an operand; lambda <= 0)
     CNT_REPROBES,              // mid-solve samples of sweep operands (policy_reprobe: Dykstra / ADMM loops)
+    CNT_TVP_FIBRES,            // general-p TV-Lp fibres solved iteratively (tvp.hip; closed forms -- copies, means -- do not count)
+    CNT_TVP_CAPPED,            // ... of which an iteration cap stopped the solve above its target gap
     CNT_COUNT
 };
 void count_event(Counter c, long n = 1);
@@ -101,12 +105,13 @@ int current_device();
 void ensure_device();
 // One-time costs belong to initialisation, not to the first solve: each translation unit's code object is uploaded to the
 // device the first time one of its kernels is touched (milliseconds apiece); ensure_device() touches one kernel per unit
-// the first time a device is used.  (Defined next to the kernels: sweep.hip, pin.hip, pinlong.hip, pointwise.hip, tv2.hip.)
+// the first time a device is used.  (Defined next to the kernels: sweep.hip, pin.hip, pinlong.hip, pointwise.hip, tv2.hip, tvp.hip.)
 void warm_sweep();
 void warm_pin();
 void warm_pinlong();
 void warm_pointwise();
 void warm_tv2();
+void warm_tvp();
 hipStream_t thread_stream();
 
 // ---- HBM scratch pool ------------------------------------------------------------------------------------------

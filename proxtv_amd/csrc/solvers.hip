@@ -18,6 +18,7 @@
 #include "policy.hpp"
 #include "sweep.hpp"
 #include "tv2.hpp"
+#include "tvp.hpp"
 
 namespace ptv {
 
@@ -62,8 +63,9 @@ long certify_fibres(const double *in, const double *out, const int *ns, int nds,
 }
 
 void prox_fibres(const double *in, double *out, const int *ns, int nds, int dim, double lam, double norm, hipStream_t s) {
-    if (norm == 2) tv2_fibres(in, out, ns, nds, dim, lam, s);
-    else           tv1_fibres(in, out, ns, nds, dim, lam, nullptr, s);
+    if (norm == 2)      tv2_fibres(in, out, ns, nds, dim, lam, s);
+    else if (norm == 1) tv1_fibres(in, out, ns, nds, dim, lam, nullptr, s);
+    else                tvp_fibres(in, out, nullptr, ns, nds, dim, lam, norm, s);   // (the entry points have checked the norm's range)
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
@@ -236,7 +238,7 @@ SolveInfo dr2_norms(size_t M, size_t N, const double *unary, double W1, double W
 SolveInfo pd2(const double *y, const double *lambdas, const double *dims, double *x, const int *ns, int nds, int npen,
               int maxIters, hipStream_t s, const double *norms) {
     SolveInfo info;
-    const bool l2a = norms && norms[0] == 2, l2b = norms && npen >= 2 && norms[1] == 2;
+    const bool l2a = norms && norms[0] != 1, l2b = norms && npen >= 2 && norms[1] != 1;   // (TV-L2 or general p: a kernel of its own)
     info.gap_set = true;
     if (maxIters <= 0) maxIters = MAX_ITERS_PD;
     const long n = total(ns, nds);
@@ -262,9 +264,9 @@ SolveInfo pd2(const double *y, const double *lambdas, const double *dims, double
     int iters = 0;
     bool settled0 = false, settled1 = false;   // (that term's sweeps are on the pinning rung, or its operand has stopped moving: no more samples of it)
     while (stop > STOP_PD && (npen > 1 || !iters) && iters < maxIters) {   // :157
-        if (l2a) {   // z = prox2(x + p) ; p += x - z     (unfused: the TV-L2 prox is its own kernel)
+        if (l2a) {   // z = prox2(x + p) ; p += x - z     (unfused: the TV-L2 and TV-Lp proxes are their own kernels)
             lincomb(po, xc, 1.0, pi, 1.0, nullptr, 0, nullptr, 0, n, s);
-            tv2_fibres(po, z.d(), ns, nds, d0, lambdas[0], s);
+            prox_fibres(po, z.d(), ns, nds, d0, lambdas[0], norms[0], s);
             lincomb(po, pi, 1.0, xc, 1.0, z.d(), -1.0, nullptr, 0, n, s);
         } else {
             if (!settled0 && reprobe_at(iters + 1)) {   // (the operand x + p is not the solve's input; the loop reads a value back every iteration anyway)
@@ -281,7 +283,7 @@ SolveInfo pd2(const double *y, const double *lambdas, const double *dims, double
         if (npen >= 2) {
             if (l2b) {
                 lincomb(qo, z.d(), 1.0, qi, 1.0, nullptr, 0, nullptr, 0, n, s);
-                tv2_fibres(qo, xn, ns, nds, d1, lambdas[1], s);
+                prox_fibres(qo, xn, ns, nds, d1, lambdas[1], norms[1], s);
                 lincomb(qo, qi, 1.0, z.d(), 1.0, xn, -1.0, nullptr, 0, n, s);
             } else {
                 if (!settled1 && reprobe_at(iters + 1)) {
@@ -370,7 +372,7 @@ SolveInfo pd_like(bool dr_variant, const double *y, const double *lambdas, const
             std::vector<double> ls((size_t)npen);
             int m = 0;
             for (int i = 0; i < npen; i++) {
-                if (norms && norms[i] == 2) continue;
+                if (norms && norms[i] != 1) continue;
                 bool dup = false;   // (several terms along one dimension share a record: the first one speaks for it)
                 for (int j = 0; j < m; j++) dup = dup || ds[(size_t)j] == (int)(dims[i] - 1);
                 if (dup) continue;
@@ -382,8 +384,8 @@ SolveInfo pd_like(bool dr_variant, const double *y, const double *lambdas, const
         }
         for (int i = 0; i < npen; i++) {
             const int d = (int)(dims[i] - 1);
-            if (norms && norms[i] == 2) {
-                tv2_fibres(z.ptr[(size_t)i], p.ptr[(size_t)i], ns, nds, d, lambdas[i], s);
+            if (norms && norms[i] != 1) {
+                prox_fibres(z.ptr[(size_t)i], p.ptr[(size_t)i], ns, nds, d, lambdas[i], norms[i], s);
                 continue;
             }
             SweepArgs a;

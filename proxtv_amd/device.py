@@ -130,25 +130,47 @@ def tv1_2d_batch(xs, w, max_iters=0, out=None):
     return y, info
 
 
-def _norms(ps, count, what="ps"):
-    """The norms of `count` terms as the C entry points take them (float64, each 1 or 2), or None for ps = None."""
-    if ps is None:
-        return None
+def _norm_array(ps, count, what):
     norms = np.array(ps, dtype=np.float64).reshape(-1)
     if norms.size != count:
         raise ValueError(f"{what}: {norms.size} norms for {count} penalties")
+    return norms
+
+
+def _norms(ps, count, what="ps"):
+    """The norms of `count` terms as the derivative calls take them (float64, each 1 or 2, whatever option general_p says), or None for
+    ps = None."""
+    if ps is None:
+        return None
+    norms = _norm_array(ps, count, what)
     if not np.all((norms == 1) | (norms == 2)):
         raise NotImplementedError(f"{what}: only p = 1 (TV-L1) and p = 2 (TV-L2) are implemented on the device, got {list(norms)}")
     return norms
 
 
+def _forward_norms(ps, count, what="ps"):
+    """The norms of `count` terms as the forward solves take them: 1 or 2, and with option general_p any 1.002 < p < 100."""
+    if ps is None:
+        return None
+    norms = _norm_array(ps, count, what)
+    if not np.all((norms == 1) | (norms == 2)):
+        try:
+            _lib.check_forward_norms(norms)
+        except NotImplementedError as e:
+            if _lib.option_value("general_p"):
+                raise NotImplementedError(f"{what}: {e}") from None
+            raise NotImplementedError(f"{what}: only p = 1 (TV-L1) and p = 2 (TV-L2) are implemented on the device, got {list(norms)}") from None
+    return norms
+
+
 def tvp_2d(x, w_col, w_row, p_col, p_row, max_iters=0, out=None):
     """Douglas-Rachford on an HBM-resident (M, N) image with the penalty ``w_col * ||diff||_{p_col}`` on every column and
-    ``w_row * ||diff||_{p_row}`` on every row, p in {1, 2} (proxtv_DR2_TVp_dev).  Returns (y, info)."""
+    ``w_row * ||diff||_{p_row}`` on every row, p in {1, 2} -- with proxtv_amd.general_p(True) any 1.002 < p < 100 (proxtv_DR2_TVp_dev).
+    Returns (y, info)."""
     _check(x, "x")
     if x.dim() != 2:
         raise ValueError(f"x: expected an (M, N) image, got {x.dim()} dimensions")
-    norms = _norms((p_col, p_row), 2, "p_col / p_row")
+    norms = _forward_norms((p_col, p_row), 2, "p_col / p_row")
     y = _out(out, x)
     info = np.zeros(_N_INFO)
     M, N = x.shape
@@ -164,7 +186,7 @@ def tvgen(x, ws, ds, max_iters=0, method=None, out=None, ps=None):
     """N-D TV-L1 on an HBM-resident column-major array.  method: None = reference dispatch (2 terms -> 'pd2',
     otherwise 'pd'); 'pdr' = parallel Douglas-Rachford; 'yang' = Yang ADMM (2-D / 3-D, one lambda per dim).
     ps (one of {1, 2} per term, or None = all 1): the norm of every term's penalty, ``w * ||diff||_p`` per fibre
-    (proxtv_PD_TVp_dev; 'pd2', 'pd' and 'pdr')."""
+    (proxtv_PD_TVp_dev; 'pd2', 'pd' and 'pdr').  With proxtv_amd.general_p(True), 'pd2' and 'pd' also take any 1.002 < p < 100."""
     _check(x, "x")
     with torch.cuda.device(x.device):
         return _tvgen(x, ws, ds, max_iters, method, _out(out, x), ps)
@@ -177,10 +199,10 @@ def _tvgen(x, ws, ds, max_iters, method, y, ps=None):
     lam = np.array(ws, dtype=np.float64)
     dims = np.array(ds, dtype=np.float64)
     npen = lam.size
-    norms = _norms(ps, npen)
     _stream = lambda: globals()["_stream"](x.device)   # noqa: E731
     if method is None:
         method = "pd2" if npen == 2 else "pd"
+    norms = _forward_norms(ps, npen) if method in ("pd2", "pd") else _norms(ps, npen)
     if norms is not None:
         if method not in ("pd2", "pd", "pdr"):
             raise NotImplementedError(f"method {method!r} takes no norms (ps goes with 'pd2', 'pd' and 'pdr')")
@@ -535,6 +557,28 @@ def tv2_fibres(x, w, dim, out=None, return_mu=False):
                                   dim, float(w), _stream(x.device))
     _lib.check("device.tv2_fibres")
     return (y, mu) if return_mu else y
+
+
+def tvp_fibres(x, w, p, dim, out=None, return_gap=False):
+    """Batched 1-D TV-Lp prox (penalty ``w * ||diff||_p`` per fibre) of every fibre of `x` along 0-based `dim`, for 1.002 < p < 100
+    (proxtv_tvpg_fibres_dev; always available, no option needed).  p = 1 and p = 2 return the bits of tv1_fibres / tv2_fibres.  With
+    `return_gap` returns (y, gap): gap, the shape of `x` without `dim`, holds every fibre's achieved duality gap (0 where the answer is a
+    closed form: a copy, the fibre's mean, p in {1, 2}); the iteration stops at 1e-8."""
+    _check(x, "x")
+    y = _out(out, x)
+    if not 0 <= int(dim) < x.dim():
+        raise ValueError(f"dim {dim} out of range for a {x.dim()}-D array")
+    dim, p = int(dim), float(p)
+    if p not in (1.0, 2.0) and not _lib.P_GENERAL_MIN < p < _lib.P_GENERAL_MAX:
+        raise NotImplementedError(f"p: the general-p solver takes {_lib.P_GENERAL_MIN} < p < {_lib.P_GENERAL_MAX}, got {p}")
+    ns = np.array(x.shape, dtype=np.int32)
+    gap = _per_fibre_empty(x.shape, dim, x.device) if return_gap else None
+    with torch.cuda.device(x.device):
+        lib = _lib.require_device()
+        lib.proxtv_tvpg_fibres_dev(x.data_ptr(), y.data_ptr(), gap.data_ptr() if return_gap and gap.numel() else 0, ns.ctypes.data, x.dim(),
+                                   dim, float(w), p, _stream(x.device))
+    _lib.check("device.tvp_fibres")
+    return (y, gap) if return_gap else y
 
 
 def tv2_fibres_vjp(y, mu, g, w, dim, need_glam=False, out=None):
