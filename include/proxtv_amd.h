@@ -201,8 +201,9 @@ int proxtv_set_option(const char *key, int value);
                     proxtv_tvp_fibres_dev, proxtv_DR2_TVp_dev, proxtv_PD_TVp_dev (which = 0, 1) take 1.002 < p < 100 (the reference's own
                     LPPROJ_PSMALL / LPPROJ_PLARGE) and serve it with the general-p fibre prox below.  The 1-D host symbols then fill
                     info[0] = outer iterations, info[1] = the achieved duality gap, info[2] = RC_OK, or RC_ITERS where the iteration cap
-                    was hit.  PDR_TV, the Yang solvers and every *_vjp entry point refuse such a norm whatever the option; p = inf and
-                    p >= 100 stay refused.  With 0 every entry point's results are what they were without the key, bit for bit. */
+                    was hit.  PDR_TV, the Yang solvers and the solver derivatives (proxtv_DR2_TVp_vjp_dev, proxtv_PD_TVp_vjp_dev) refuse
+                    such a norm whatever the option -- the fibre prox alone has its derivative, proxtv_tvpg_fibres_vjp_dev; p = inf
+                    and p >= 100 stay refused.  With 0 every entry point's results are what they were without the key, bit for bit. */
 
 /* Device-pointer solvers: every double* is an HBM pointer valid on the current device, `stream` is
    a hipStream_t (NULL = the library's per-thread stream), `info` is a HOST double[3] or NULL.
@@ -379,6 +380,32 @@ int proxtv_DR2_TVp_dev(size_t M, size_t N, const double *unary, double W1, doubl
    returns 1, or 0 with proxtv_last_error set. */
 int proxtv_tvpg_fibres_dev(const double *in, double *out, double *gap /*or NULL*/, const int *ns /*host*/, int nds, int dim, double lambda,
                            double p, void *stream);
+
+/* The derivative of that prox for a general p (1.002 < p < 100, p != 2): y is what proxtv_tvpg_fibres_dev returned for the same ns / dim /
+   lambda / p -- the output, lambda and p are all it needs: no multiplier, no tape.  Per fibre of n samples, D the (n-1) x n difference
+   matrix, T = D D', w = D y, N = ||w||_p, s_i = |w_i| / N, q = p / (p - 1), phi_i = sign(w_i) s_i^(p-1), a cotangent g:
+     J = (I + lambda D' H D)^-1,  H = (p-1)/N (diag s^(p-2) - phi phi'), applied in the arm where every power has an exponent >= 0
+     p > 2       M = I + lambda D' diag((p-1)/N s^(p-2)) D,  b = D' phi,  c = lambda (p-1) / N,  a = M^-1 g,  e = M^-1 b
+                 gx = a + c (b'a) / (1 - c b'e) e                           (shape of y; gx may be g itself)
+     p < 2       H = T + diag((q-1) N / lambda s^(2-p)),  h = D g,  a = H^-1 h,  e = H^-1 w
+                 gx = g - D'(a - (w'a) / (w'e) e)
+     both        glam = -gx' D' phi                                         (glam or NULL: DEVICE double per fibre, laid out as gap; for one
+                                                                             lambda shared by all fibres d/dlambda is the sum of glam)
+     y constant along the fibre (N == 0 exactly):  gx = mean(g) on every sample, glam = 0
+     ns[dim] == 1 or lambda <= 0:  gx = g, glam = 0
+   The Jacobian is symmetric, so this one call is the VJP and the JVP in x.  The branch the forward took is what is differentiated: where
+   it answered with the fibre's mean (the dual inside the ball, or its capped fall-back) it stored the mean itself on every sample, and
+   that is what N == 0 recognises.  Four passes per fibre -- the largest |w_i|, N, one forward elimination of the tridiagonal matrix on both
+   right-hand sides, which also yields both scalar products, one backward substitution on the combined vector -- against the forward's
+   30-100.  One lane per fibre, a single long fibre on one lane, as in the forward.  Scratch comes from the pool -- three arrays of the
+   data's size, five along dimension 0; beyond the pool's cap (PROXTV_POOL_CAP_MB) the call is refused and proxtv_last_error names the
+   bytes.  A total size of 0: returns 1, nothing is written.  A missing y / g / gx, a dimension out of range, any overlap except gx == g,
+   or a p this solver does not take -- p = 1 and p = 2 among them: their derivatives are proxtv_tv1_fibres_vjp_dev and
+   proxtv_tv2_fibres_vjp_dev -- returns 0 with proxtv_last_error set and nothing written.  No atomics: a fibre's bits depend on that fibre
+   alone and the same call gives the same bits.  Synchronises the stream; returns 1 on success.  A general p inside the solver derivatives
+   (proxtv_DR2_TVp_vjp_dev, proxtv_PD_TVp_vjp_dev) stays refused. */
+int proxtv_tvpg_fibres_vjp_dev(const double *y, const double *g, double *gx /*may be g*/, double *glam /*device, one per fibre, or NULL*/,
+                               const int *ns /*host*/, int nds, int dim, double lambda, double p, void *stream);
 
 /* The TV-L2 fibre prox on its own, with its multiplier: out = argmin 1/2 ||x - in||^2 + lambda ||Dx||_2 along `dim` of every fibre --
    the bits of proxtv_tvp_fibres_dev(p = 2).  Per fibre of n samples, D the (n-1) x n difference matrix and T = D D' = tridiag(-1, 2, -1):

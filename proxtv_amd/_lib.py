@@ -89,6 +89,7 @@ SIGNATURES = {
     "proxtv_DR2_TV_batch": (C.c_int, [C.c_size_t, C.c_size_t, C.c_size_t, _dp, C.c_double, C.c_double, _dp, C.c_int, _dp]),
     "proxtv_tvp_fibres_dev": (C.c_int, [_dp, _dp, _ip, C.c_int, C.c_int, C.c_double, C.c_double, C.c_void_p]),
     "proxtv_tvpg_fibres_dev": (C.c_int, [_dp, _dp, _dp, _ip, C.c_int, C.c_int, C.c_double, C.c_double, C.c_void_p]),
+    "proxtv_tvpg_fibres_vjp_dev": (C.c_int, [_dp, _dp, _dp, _dp, _ip, C.c_int, C.c_int, C.c_double, C.c_double, C.c_void_p]),
     "proxtv_tv2_fibres_dev": (C.c_int, [_dp, _dp, _dp, _ip, C.c_int, C.c_int, C.c_double, C.c_void_p]),
     "proxtv_tv2_fibres_vjp_dev": (C.c_int, [_dp, _dp, _dp, _dp, _dp, _ip, C.c_int, C.c_int, C.c_double, C.c_void_p]),
     "proxtv_DR2_TVp_dev": (C.c_int, [C.c_size_t, C.c_size_t, _dp, C.c_double, C.c_double, C.c_double, C.c_double, _dp, C.c_int,

@@ -17,6 +17,8 @@ tv2_fibres(x, w, dim) is device.tv2_fibres with ONE device.tv2_fibres_vjp call a
 differentiated solver families are covered too: tvp_2d(x, w_col, w_row, p_col, p_row) is device.tvp_2d with ONE
 device.dr2_vjp(..., p_col=, p_row=) call as backward, and tvgen(..., ps=[...]) is device.tvgen(..., ps=) with ONE
 device.tvgen_vjp(..., ps=) call; every p is 1 or 2.  At a TV-L2 fibre's kink the branch the forward sweep took is differentiated.
+The general-p fibre prox alone has its derivative too: tvp_fibres(x, w, p, dim) is device.tvp_fibres with ONE device.tvp_fibres_vjp call
+as backward, from the saved output alone; a general p inside tvp_2d / tvgen stays refused.
 
     y = autograd.tvgen(x, [w0, w1, w2], [1, 2, 3])   # a volume; every w a float or a 0-d float64 tensor
     y = autograd.tvgen(x, [w0, w1, w2], [1, 2, 3], ps=[1, 2, 1])
@@ -102,6 +104,42 @@ def tv2_fibres(x, w, dim):
     if not _wants(x, w):
         return device.tv2_fibres(x, float(w), dim)
     return _TV2Fibres.apply(x, w, int(dim))
+
+
+class _TVpFibres(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, w, p, dim):
+        y = device.tvp_fibres(_colmajor(x.detach()), float(w), p, dim)
+        ctx.save_for_backward(y)
+        ctx.dim, ctx.w, ctx.p = dim, float(w), p
+        ctx.w_device = w.device if isinstance(w, torch.Tensor) else None
+        return y
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, gy):
+        (y,) = ctx.saved_tensors
+        need_x, need_w = ctx.needs_input_grad[:2]
+        res = device.tvp_fibres_vjp(y, gy, ctx.w, ctx.p, ctx.dim, need_glam=need_w)
+        gx, glam = res if need_w else (res, None)
+        return (gx if need_x else None), (glam.sum().to(ctx.w_device) if need_w else None), None, None
+
+
+def tvp_fibres(x, w, p, dim):
+    """``device.tvp_fibres(x, w, p, dim)`` (the TV-Lp fibre prox, penalty ``w * ||diff||_p`` per fibre, 1.002 < p < 100) with a graph
+    behind it: differentiable in x, and in w when w is a 0-d float64 tensor (its gradient comes back on that tensor's device); p is a
+    plain number and is not differentiated.  The forward is bit for bit device.tvp_fibres's and saves its output alone; backward is ONE
+    device.tvp_fibres_vjp call plus, for w, a sum (the branch the forward took is differentiated).  p = 1 and p = 2 are
+    tv1_fibres and tv2_fibres.  When nothing asks for a gradient this IS device.tvp_fibres."""
+    _scalar_penalty(w, "w")
+    p = float(p)
+    if p == 1.0:
+        return tv1_fibres(x, w, dim)
+    if p == 2.0:
+        return tv2_fibres(x, w, dim)
+    if not _wants(x, w):
+        return device.tvp_fibres(x, float(w), p, dim)
+    return _TVpFibres.apply(x, w, p, int(dim))
 
 
 class _DR2(torch.autograd.Function):

@@ -14,6 +14,7 @@
 #include "sweep.hpp"
 #include "tv2.hpp"
 #include "tvp.hpp"
+#include "tvp_vjp.hpp"
 
 using namespace ptv;
 
@@ -956,6 +957,37 @@ int proxtv_tv2_fibres_vjp_dev(const double *y, const double *mu, const double *g
         }
         hipStream_t st = pick(stream);
         tv2_fibres_vjp(y, mu, g, gx, glam, ns, nds, dim, lambda, st);
+        PTV_HIP(hipStreamSynchronize(st));
+    });
+}
+
+int proxtv_tvpg_fibres_vjp_dev(const double *y, const double *g, double *gx, double *glam, const int *ns, int nds, int dim, double lambda,
+                               double p, void *stream) {
+    return guarded("proxtv_tvpg_fibres_vjp_dev", nullptr, 1, [&] {
+        if (dim < 0 || dim >= nds) reject("dimension out of range");
+        if (p == 1) reject("p = 1 has its own derivative: proxtv_tv1_fibres_vjp_dev");
+        if (p == 2) reject("p = 2 has its own derivative: proxtv_tv2_fibres_vjp_dev");
+        if (!tvp_general_norm(p)) reject("the general-p derivative takes 1.002 < p < 100; other norms are not implemented on the HIP path");
+        const size_t n = (size_t)total(ns, nds);
+        if (n == 0) return;
+        if (!y || !g || !gx) reject("y, g and gx are required");
+        // every array is read while others are written: none may overlap another, except that gx may BE g (tvpvjpcore.hpp)
+        const size_t nf = n / (size_t)ns[dim];
+        struct Span { const double *p; size_t n; bool out; const char *name; };
+        const Span spans[] = {{y, n, false, "y"}, {g, n, false, "g"}, {gx, n, true, "gx"}, {glam, nf, true, "glam"}};
+        for (const Span &o : spans) {
+            if (!o.out || !o.p) continue;
+            for (const Span &i : spans) {
+                if (&i == &o || (&o == &spans[2] && &i == &spans[1] && gx == g)) continue;
+                if (i.out && &i > &o) continue;   // (a pair of outputs: once)
+                if (spans_overlap(i.p, i.n, o.p, o.n)) {
+                    set_error("%s overlaps %s (only gx may alias g, and then exactly)", o.name, i.name);
+                    throw HipFailure{hipErrorInvalidValue};
+                }
+            }
+        }
+        hipStream_t st = pick(stream);
+        tvp_fibres_vjp(y, g, gx, glam, ns, nds, dim, lambda, p, st);
         PTV_HIP(hipStreamSynchronize(st));
     });
 }

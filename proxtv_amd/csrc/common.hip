@@ -136,6 +136,7 @@ static void probe_device(int dev) {
         warm_pointwise();
         warm_tv2();
         warm_tvp();
+        warm_tvp_vjp();
     } catch (const HipFailure &) {
         (void)hipGetLastError();   // not fatal: the first launch will load (or report) what this could not
         set_error("%s", before.c_str());   // ... and PTV_HIP recorded a message before it threw: a solve that then succeeds must not report it

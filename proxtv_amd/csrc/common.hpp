@@ -105,13 +105,14 @@ int current_device();
 void ensure_device();
 // One-time costs belong to initialisation, not to the first solve: each translation unit's code object is uploaded to the
 // device the first time one of its kernels is touched (milliseconds apiece); ensure_device() touches one kernel per unit
-// the first time a device is used.  (Defined next to the kernels: sweep.hip, pin.hip, pinlong.hip, pointwise.hip, tv2.hip, tvp.hip.)
+// the first time a device is used.  (Defined next to the kernels: sweep.hip, pin.hip, pinlong.hip, pointwise.hip, tv2.hip, tvp.hip, tvp_vjp.hip.)
 void warm_sweep();
 void warm_pin();
 void warm_pinlong();
 void warm_pointwise();
 void warm_tv2();
 void warm_tvp();
+void warm_tvp_vjp();
 hipStream_t thread_stream();
 
 // ---- HBM scratch pool ------------------------------------------------------------------------------------------

@@ -619,6 +619,44 @@ def tv2_fibres_vjp(y, mu, g, w, dim, need_glam=False, out=None):
     return (gx, glam) if need_glam else gx
 
 
+def tvp_fibres_vjp(y, g, w, p, dim, need_glam=False, out=None):
+    """The derivative of ``y = tvp_fibres(x, w, p, dim)`` for a general p (1.002 < p < 100, p != 2) applied to `g`: returns gx, or
+    (gx, glam) with `need_glam`.  It reads the prox's output, w and p only.
+
+    Per fibre, with D the difference matrix, d = D y, N = ||d||_p, s = |d| / N and phi = sign(d) s^(p-1): gx = J g with the symmetric
+    J = (I + w D' H D)^-1, H = (p-1)/N (diag s^(p-2) - phi phi') -- two solves with one tridiagonal matrix (n x n for p > 2,
+    (n-1) x (n-1) for p < 2) and a rank-one correction -- and glam = -gx'D'phi.  Where y is constant along the fibre (the forward answered
+    with the mean) gx is the mean of g and glam = 0; for an extent of 1 and for w <= 0, gx = g.  glam holds one value per fibre (the shape
+    of `y` without `dim`); for one w shared by all fibres d/dw is ``glam.sum()``.  The branch the forward took is what is differentiated
+    (include/proxtv_amd.h: proxtv_tvpg_fibres_vjp_dev).  p = 1 and p = 2 have their own derivatives, tv1_fibres_vjp and
+    tv2_fibres_vjp, which need other inputs.  A `g` in another layout is copied; `out` may be `g`."""
+    _check(y, "y")
+    if not 0 <= int(dim) < y.dim():
+        raise ValueError(f"dim {dim} out of range for a {y.dim()}-D array")
+    dim, p = int(dim), float(p)
+    if p in (1.0, 2.0):
+        raise ValueError(f"p = {p:g} has its own derivative: {'tv1_fibres_vjp' if p == 1.0 else 'tv2_fibres_vjp'}")
+    if not _lib.P_GENERAL_MIN < p < _lib.P_GENERAL_MAX:
+        raise NotImplementedError(f"p: the general-p derivative takes {_lib.P_GENERAL_MIN} < p < {_lib.P_GENERAL_MAX}, got {p}")
+    if not (isinstance(g, torch.Tensor) and g.is_cuda and g.dtype == torch.float64):
+        raise ValueError("g: expected a float64 CUDA tensor")
+    if g.device != y.device:
+        raise ValueError(f"g: lives on {g.device}, the input on {y.device}")
+    if tuple(g.shape) != tuple(y.shape):
+        raise ValueError(f"g: shape {tuple(g.shape)}, expected {tuple(y.shape)}")
+    if not _is_colmajor(g):
+        g = to_colmajor(g)
+    gx = _out(out, y)
+    ns = np.array(y.shape, dtype=np.int32)
+    glam = _per_fibre_empty(y.shape, dim, y.device) if need_glam else None
+    ptr = lambda t: t.data_ptr() if t is not None and t.numel() else 0   # noqa: E731
+    with torch.cuda.device(y.device):
+        lib = _lib.require_device()
+        lib.proxtv_tvpg_fibres_vjp_dev(ptr(y), ptr(g), ptr(gx), ptr(glam), ns.ctypes.data, y.dim(), dim, float(w), p, _stream(y.device))
+    _lib.check("device.tvp_fibres_vjp")
+    return (gx, glam) if need_glam else gx
+
+
 def tv1_fibres_dof(y, dim):
     """Segments of every fibre of ``y = tv1_fibres(x, w, dim)`` along `dim` (int32, the shape of `y` without `dim`): the trace of the
     prox's Jacobian, i.e. the degrees of freedom SURE needs.  One pass over `y`; nothing else is computed."""
