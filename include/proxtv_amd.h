@@ -201,9 +201,16 @@ int proxtv_set_option(const char *key, int value);
                     proxtv_tvp_fibres_dev, proxtv_DR2_TVp_dev, proxtv_PD_TVp_dev (which = 0, 1) take 1.002 < p < 100 (the reference's own
                     LPPROJ_PSMALL / LPPROJ_PLARGE) and serve it with the general-p fibre prox below.  The 1-D host symbols then fill
                     info[0] = outer iterations, info[1] = the achieved duality gap, info[2] = RC_OK, or RC_ITERS where the iteration cap
-                    was hit.  PDR_TV, the Yang solvers and the solver derivatives (proxtv_DR2_TVp_vjp_dev, proxtv_PD_TVp_vjp_dev) refuse
-                    such a norm whatever the option -- the fibre prox alone has its derivative, proxtv_tvpg_fibres_vjp_dev; p = inf
-                    and p >= 100 stay refused.  With 0 every entry point's results are what they were without the key, bit for bit. */
+                    was hit.  PDR_TV and the Yang solvers refuse such a norm whatever the option; the solver derivatives
+                    (proxtv_DR2_TVp_vjp_dev, proxtv_PD_TVp_vjp_dev) refuse it unless general_p_vjp, below -- the fibre prox's own
+                    derivative, proxtv_tvpg_fibres_vjp_dev, needs no option; p = inf and p >= 100 stay refused.  With 0 every entry
+                    point's results are what they were without the key, bit for bit.
+     general_p_vjp  (environment: PROXTV_GENERAL_P_VJP) 0 (default): the solver derivatives refuse a norm outside {1, 2}, as they always
+                    have ; 1: proxtv_DR2_TVp_vjp_dev and proxtv_PD_TVp_vjp_dev take 1.002 < p < 100 per direction / term (below).  The
+                    calls replay the forward themselves: general_p is not asked.  With 1 and every norm in {1, 2} they run the launches
+                    and return the bits of 0.
+     tvp_vjp_route  debugging aid: where the write-out of a general-p reverse sweep runs -- 0 (default) by the fibre count, 1 inside the
+                    fibre kernel wherever legal, 2 as a pointwise pass behind the plain kernel everywhere.  The same bits all three. */
 
 /* Device-pointer solvers: every double* is an HBM pointer valid on the current device, `stream` is
    a hipStream_t (NULL = the library's per-thread stream), `info` is a HOST double[3] or NULL.
@@ -403,7 +410,7 @@ int proxtv_tvpg_fibres_dev(const double *in, double *out, double *gap /*or NULL*
    or a p this solver does not take -- p = 1 and p = 2 among them: their derivatives are proxtv_tv1_fibres_vjp_dev and
    proxtv_tv2_fibres_vjp_dev -- returns 0 with proxtv_last_error set and nothing written.  No atomics: a fibre's bits depend on that fibre
    alone and the same call gives the same bits.  Synchronises the stream; returns 1 on success.  A general p inside the solver derivatives
-   (proxtv_DR2_TVp_vjp_dev, proxtv_PD_TVp_vjp_dev) stays refused. */
+   (proxtv_DR2_TVp_vjp_dev, proxtv_PD_TVp_vjp_dev) is refused unless option general_p_vjp. */
 int proxtv_tvpg_fibres_vjp_dev(const double *y, const double *g, double *gx /*may be g*/, double *glam /*device, one per fibre, or NULL*/,
                                const int *ns /*host*/, int nds, int dim, double lambda, double p, void *stream);
 
@@ -460,7 +467,19 @@ int proxtv_PD_TVp_dev(int which, const double *y, const double *lambdas_scaled, 
    cap, summed over the directions / terms d, with n the array's size, K the sweeps per term (DR: maxit + 1; PD: iters; PD2 with one
    term: 1), words_d = proxtv_tv1_steps_words along d and fibres_d = n / ns[d]:
        TV-L1, tape = 0:  8 K n          TV-L1, tape = 1:  8 n + 4 K words_d          TV-L2, either tape:  8 K (n + fibres_d)
-   Every result is the same bits for both tapes.  No atomics: the same call gives the same bits. */
+       a general p, either tape:  8 K n
+   Every result is the same bits for both tapes.  No atomics: the same call gives the same bits.
+   With option general_p_vjp = 1 a norm may also be any 1.002 < p < 100 (p = inf, p >= 100 and p <= 1.002 stay refused and the error
+   names the range; with the option 0 every such norm is refused as before).  Such a sweep is proxtv_tvpg_fibres_dev's forward and
+   proxtv_tvpg_fibres_vjp_dev's derivative -- from the sweep's output, lambda and p alone -- with the recurrence's pointwise work inside
+   that kernel or in one pointwise pass behind it (always for dimension-0 fibres; the same bits either way).  It keeps its float64 output
+   and nothing else, under either tape.  glam for such a term is the sum over the fibres of proxtv_tvpg_fibres_vjp_dev's glam.  The branch
+   rule is that call's, sweep by sweep: a constant output fibre differentiates as the mean, ns[d] == 1 or lambda <= 0 as the identity, a
+   fibre the forward's iteration cap stopped at the output it returned.  Before anything runs, three sizes are held against the pool's cap
+   and a call beyond it is refused with the bytes named and nothing written: the tape (above); per general-p term its forward scratch,
+   8 n * 4 (8 n * 6 along dimension 0 of several fibres) + 12 fibres_d + 32; and its reverse scratch, 8 n * 3 (8 n * 5 along dimension 0
+   of several fibres), plus, where the write-out is a pass of its own, 8 n (16 n for which = 1) and 8 fibres_d when glam is asked for.
+   Not differentiated: the iteration count, p itself, the forward's stopping error. */
 int proxtv_DR2_TVp_vjp_dev(size_t M, size_t N, const double *unary, double W1, double W2, double norm1, double norm2, const double *g,
                            double *s /*or NULL*/, double *gU, double *glam /*host double[2], or NULL*/, int maxit, int tape, void *stream);
 int proxtv_PD_TVp_vjp_dev(int which, const double *y, const double *lambdas, const double *norms /*host, or NULL*/, const double *dims,

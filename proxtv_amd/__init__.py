@@ -34,7 +34,7 @@ import numpy as np
 from . import _lib
 from ._lib import ProxTVError  # noqa: F401
 
-__all__ = ["general_p", "tv1_1d", "tv1w_1d", "tv2_1d", "tvp_1d", "tv1_2d", "tv1w_2d", "tvp_2d", "tvgen", "tv1_2d_batch",
+__all__ = ["general_p", "general_p_vjp", "tv1_1d", "tv1w_1d", "tv2_1d", "tvp_1d", "tv1_2d", "tv1w_2d", "tvp_2d", "tvgen", "tv1_2d_batch",
            "force_float_scalar", "force_float_matrix", "ProxTVError"]
 
 # The maximum number of returned info parameters (reference: prox_tv/__init__.py:67).
@@ -63,6 +63,13 @@ def force_float_matrix(x):
     if x.dtype != np.dtype("float64"):
         return x.astype("float")
     return x
+
+
+def general_p_vjp(on):
+    """Switch the solver derivatives for a general norm on or off: device.dr2_vjp(p_col=, p_row=) / device.tvgen_vjp(ps=) then take any
+    1.002 < p < 100 (proxtv_set_option("general_p_vjp", ...); process-wide, off by default; environment: PROXTV_GENERAL_P_VJP=1).
+    autograd.tvp_2d / autograd.tvgen(ps=) want general_p(True) as well: their forward is the fused solve.  Returns the previous setting."""
+    return bool(_lib.load().proxtv_set_option(b"general_p_vjp", 1 if on else 0))
 
 
 def general_p(on):

@@ -193,6 +193,27 @@ def check_forward_norms(ps):
         raise NotImplementedError(f"the general-p solver takes {P_GENERAL_MIN} < p < {P_GENERAL_MAX}, got {bad}")
 
 
+def check_vjp_norms(ps, forward_too=False):
+    """The norms a solver derivative takes: 1 and 2 always; with option general_p_vjp (proxtv_amd.general_p_vjp) any 1.002 < p < 100.
+    `forward_too`: the caller's forward is the fused solve (autograd), which wants option general_p as well -- the error names the
+    option that is missing.  Raises the NotImplementedError the package has always raised for the others."""
+    others = [float(p) for p in ps if p not in (1, 2)]
+    if not others:
+        return
+    have_vjp, have_fwd = bool(option_value("general_p_vjp")), bool(option_value("general_p"))
+    if not have_vjp and not (forward_too and have_fwd):
+        raise NotImplementedError(_ONLY_P12)
+    if not have_vjp:
+        raise NotImplementedError(f"a gradient through norms {others} needs option general_p_vjp as well (proxtv_amd.general_p_vjp(True)): "
+                                  "general_p alone covers the forward solve")
+    if forward_too and not have_fwd:
+        raise NotImplementedError(f"a forward solve with norms {others} needs option general_p as well (proxtv_amd.general_p(True)): "
+                                  "general_p_vjp alone covers device.dr2_vjp / device.tvgen_vjp")
+    bad = [p for p in others if not P_GENERAL_MIN < p < P_GENERAL_MAX]
+    if bad:
+        raise NotImplementedError(f"the solver derivatives take {P_GENERAL_MIN} < p < {P_GENERAL_MAX}, got {bad}")
+
+
 def last_error():
     msg = load().proxtv_last_error()
     return msg.decode() if msg else ""

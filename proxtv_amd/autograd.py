@@ -252,11 +252,13 @@ def tvp_2d(x, w_col, w_row, p_col, p_row, max_iters=0, tape="outputs"):
     """``device.tvp_2d(x, w_col, w_row, p_col, p_row, max_iters)[0]`` (Douglas-Rachford with a TV-L1 or TV-L2 penalty per direction, p in
     {1, 2}) with a graph behind it: differentiable in x and in w_col / w_row where they are 0-d float64 tensors (the gradient comes back on
     that tensor's device; one tensor for both receives the sum).  The result is bit for bit device.tvp_2d's; backward is ONE
-    device.dr2_vjp call.  When nothing asks for a gradient this IS device.tvp_2d."""
+    device.dr2_vjp call.  When nothing asks for a gradient this IS device.tvp_2d.  A general p (1.002 < p < 100) needs
+    both proxtv_amd.general_p(True), for the fused forward solve, and proxtv_amd.general_p_vjp(True), for backward; the
+    error names the one that is missing."""
     _scalar_penalty(w_col, "w_col")
     _scalar_penalty(w_row, "w_row")
     device._tape(tape)
-    device._norms((p_col, p_row), 2, "p_col / p_row")
+    device._norms((p_col, p_row), 2, "p_col / p_row", forward_too=True)
     if not _wants(x, w_col, w_row):
         return device.tvp_2d(x, float(w_col), float(w_row), p_col, p_row, max_iters)[0]
     return _DR2p.apply(x, w_col, w_row, (float(p_col), float(p_row), int(max_iters), tape))
@@ -297,9 +299,10 @@ def tvgen(x, ws, ds, max_iters=0, method=None, tape="outputs", ps=None):
     method: None (tvgen's dispatch), 'pd2' or 'pd'; 'pdr' and 'yang' raise NotImplementedError when a gradient is asked for.  The result
     is bit for bit device.tvgen's; when nothing asks for a gradient this IS device.tvgen.  Backward differentiates the iterations the
     forward ran (its info[0]), not the dependence of their number on the data.  ps (one of {1, 2} per term, or None = all 1): the norm
-    of every term's penalty, as device.tvgen takes it."""
+    of every term's penalty, as device.tvgen takes it; a general p (1.002 < p < 100) needs both proxtv_amd.general_p(True)
+    and proxtv_amd.general_p_vjp(True)."""
     ws = list(ws)
-    ps = None if ps is None else tuple(float(p) for p in device._norms(ps, len(ws)))
+    ps = None if ps is None else tuple(float(p) for p in device._norms(ps, len(ws), forward_too=True))
     for i, w in enumerate(ws):
         _scalar_penalty(w, f"ws[{i}]")
     device._tape(tape)

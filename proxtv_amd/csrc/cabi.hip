@@ -157,6 +157,39 @@ bool check_norms(const double *norms, int npen, bool general = false) {
     return other;
 }
 
+// The norms of a solver derivative: 1 or 2, and only with option general_p_vjp any 1.002 < p < 100 (the calls replay the forward
+// themselves: option general_p is not asked).  Returns whether any term is not TV-L1; throws the refusal otherwise -- with the option
+// off, the one every such norm has always got.
+bool check_vjp_norms(const double *norms, int npen) {
+    bool other = false;
+    for (int i = 0; i < npen; i++) {
+        const double p = norms[i];
+        if (p != 1 && p != 2) {
+            if (!options().general_p_vjp) reject(kOnlyP12);
+            if (!tvp_general_norm(p))
+                reject("option general_p_vjp: the solver derivatives take 1.002 < p < 100; other norms are not implemented on the HIP path");
+        }
+        other = other || p != 1;
+    }
+    return other;
+}
+
+// the scratch of one term's general-p sweeps, forward and in reverse (write-out `mode`), against the pool's cap: before anything runs
+void check_tvp_sweep_scratch(const int *ns, int nds, int dim, double p, int mode, bool with_glam) {
+    if (p == 1 || p == 2) return;
+    const size_t fwd = tvp_scratch_bytes(ns, nds, dim), rev = tvp_vjp_epi_scratch_bytes(ns, nds, dim, mode, with_glam);
+    if (fwd > pool_cap_bytes()) {
+        set_error("a general-p sweep along dimension %d needs %zu bytes of scratch forward, the scratch pool is capped at %zu (PROXTV_POOL_CAP_MB)",
+                  dim + 1, fwd, pool_cap_bytes());
+        throw HipFailure{hipErrorOutOfMemory};
+    }
+    if (rev > pool_cap_bytes()) {
+        set_error("a general-p sweep along dimension %d needs %zu bytes of scratch in reverse, the scratch pool is capped at %zu (PROXTV_POOL_CAP_MB)",
+                  dim + 1, rev, pool_cap_bytes());
+        throw HipFailure{hipErrorOutOfMemory};
+    }
+}
+
 // the general-p prox of one host signal: info as the reference's TV-Lp solvers fill it (iterations, gap, RC_OK / RC_ITERS)
 void tvp1d_host(const double *y, double lam, double *x, int n, double p, double *info) {
     TvpStats st;
@@ -766,7 +799,7 @@ static int dr2_vjp_entry(const char *who, size_t M, size_t N, size_t B, const do
     return guarded(who, nullptr, 1, [&] {
         if (tape != 0 && tape != 1) reject("tape: 0 (sweep outputs) or 1 (step codes)");
         const double nrm[2] = {norm1, norm2};
-        check_norms(nrm, 2);
+        check_vjp_norms(nrm, 2);
         const size_t n = M * N * B;
         if (n == 0) return;
         if (M > 0x7fffffffu || N > 0x7fffffffu || B > 65535u) reject("image extents beyond 2^31 - 1 or more than 65535 images");
@@ -792,6 +825,11 @@ static int dr2_vjp_entry(const char *who, size_t M, size_t N, size_t B, const do
         if (need > pool_cap_bytes()) {
             set_error("the tape of sweep outputs needs %zu bytes, the scratch pool is capped at %zu (PROXTV_POOL_CAP_MB)", need, pool_cap_bytes());
             throw HipFailure{hipErrorOutOfMemory};
+        }
+        {
+            const int ns[3] = {(int)M, (int)N, (int)B};
+            check_tvp_sweep_scratch(ns, 3, 0, norm1, TV2_VJP_DR_COL, glam != nullptr);
+            check_tvp_sweep_scratch(ns, 3, 1, norm2, TV2_VJP_DR_ROW, glam != nullptr);
         }
         hipStream_t st = pick(stream);
         SolveScope scope(st);
@@ -820,7 +858,7 @@ static int pd_vjp_entry(const char *who, int which, const double *y, const doubl
         if (iters < 1) reject("iters: the iteration count of the forward solve (info[0]), at least 1");
         if (npen < 1) reject("at least one penalty term is required");
         if (which == 0 && npen > 2) reject("PD2 works with 1 or 2 penalties");
-        if (norms && !check_norms(norms, npen)) norms = nullptr;   // (every term TV-L1: the call without norms)
+        if (norms && !check_vjp_norms(norms, npen)) norms = nullptr;   // (every term TV-L1: the call without norms)
         check_dims(dims, npen, nds);
         const size_t n = (size_t)total(ns, nds);
         if (n == 0) return;
@@ -844,6 +882,9 @@ static int pd_vjp_entry(const char *who, int which, const double *y, const doubl
             set_error("the tape of sweep outputs needs %zu bytes, the scratch pool is capped at %zu (PROXTV_POOL_CAP_MB)", need, pool_cap_bytes());
             throw HipFailure{hipErrorOutOfMemory};
         }
+        for (int i = 0; norms && i < npen; i++)
+            check_tvp_sweep_scratch(ns, nds, (int)(dims[i] - 1), norms[i], which == 1 ? TV2_VJP_PD : (npen == 1 ? TV2_VJP_PLAIN : TV2_VJP_PD2),
+                                    glam != nullptr);
         hipStream_t st = pick(stream);
         SolveScope scope(st);
         pd_vjp(which, y, lambdas, dims, ns, nds, npen, iters, g, x, gy, glam, tape, st, norms);

@@ -47,6 +47,8 @@ constexpr OptionEntry kOptionTable[] = {
     {"why", &Options::why},
     {"trace", &Options::trace},
     {"general_p", &Options::general_p},
+    {"general_p_vjp", &Options::general_p_vjp},
+    {"tvp_vjp_route", &Options::tvp_vjp_route},
     {"ablate", &Options::ablate},
     {"debug_legacy_rebuild", &Options::debug_legacy_rebuild},
 };

@@ -70,6 +70,10 @@ struct Options {
     int ablate = 0;     // profiling aid, see ChunkPlan::ablate (results are WRONG when non-zero)
     int general_p = 0;        // 1: the reference's entry points take a general norm (1.002 < p < 100) and serve it with tvp.hip; 0 (default): they
                               // refuse every p outside {1, 2}, as they always have (proxtv_tvpg_fibres_dev takes it either way)
+    int general_p_vjp = 0;    // 1: the solver derivatives (proxtv_DR2_TVp_vjp_dev, proxtv_PD_TVp_vjp_dev) take a general norm (1.002 < p < 100) and
+                              // differentiate its sweeps with tvp_vjp.hip; 0 (default): they refuse every p outside {1, 2}, as they always have
+    int tvp_vjp_route = 0;    // debugging aid: the write-out of a general-p reverse sweep -- 0 = by the fibre count (policy.hpp), 1 = inside the
+                              // fibre kernel wherever legal, 2 = a pointwise pass behind the plain kernel everywhere; the same bits all three
     int debug_legacy_rebuild = 0;   // test aid: the along-fibre kernel's rebuild with the semantics of rounds 1-4 (an unproven chunk values its first
                                     // piece from its own first row) -- results MAY BE WRONG; exists so that the suite can watch `certify` catch it
 };

@@ -47,6 +47,17 @@ constexpr int kMonitorLag = 2;      // family sweeps between a steady-state samp
 constexpr int kHoldSolves = 2;      // solves during which a rejected direction is not tried again
 constexpr int kQuietSolves = 16;    // one-sweep solves between explorations
 
+// The general-p derivative as a sweep of a solver's reverse recurrence (tvp_vjp.hip): whether the write-out runs inside
+// the lane-per-fibre kernel (fused) or as a pointwise pass behind the plain kernel (epilogue), where both are legal.  A threshold on the
+// fibre count: few fibres are few latency-bound waves, which the write-out's extra loads and stores lengthen one by one, while the
+// pointwise pass runs at bandwidth; many fibres might hide them, and the fused kernel saves a pass over the arrays.  Measured in pairs of
+// whole calls (profiles/tvpg_vjp_time.txt, DESIGN.md 6j has the figures): at 16384 fibres x 1024 samples the fused route is slower by
+// 0.7 / 1.0 ms of a 2 ms sweep (p = 1.5 / 3: medians of 40 pairs, both quartiles positive); at 4096 x 4096 and at 262144 x 64 the
+// medians say the same or nothing, inside the spread of the forward sweep that every call contains.  At no count measured is the fused route faster, so no count switches
+// it on: it runs on request (option tvp_vjp_route = 1), where it needs one or two arrays of scratch less.
+constexpr long kTvpVjpFusedMinFibres = -1;   // fused from this many fibres on; negative: at no count
+inline bool tvp_vjp_fused_auto(long fibres) { return kTvpVjpFusedMinFibres >= 0 && fibres >= kTvpVjpFusedMinFibres; }
+
 // Seeding.  Before a solve the input's edges |y_k - y_{k-1}| are sampled along every dimension it sweeps (pointwise.hip's
 // edge_histogram); the fraction f of them above 4 lambda -- the edges at which the string is KNOWN to bend
 // (chunkcore.hpp) -- says which rung the data want: on unit noise f = 0.78 / 0.40 / 0.16 / 0.05 / 0.005 at lambda = 0.1 /

@@ -1,6 +1,8 @@
 // tv2.hpp -- batched exact 1-D TV-L2 prox over fibres (tv2.hip) and its derivative (tv2_vjp.hip).
 #pragma once
 
+#include <memory>
+
 #include "common.hpp"
 
 namespace ptv {
@@ -41,6 +43,34 @@ struct Tv2VjpEpi {
 // front, which forms pi with the same fma).
 void tv2_fibres_vjp_epi(const double *y, const double *mu, const double *g, double *gx, double *glam, const int *ns, int nds, int dim,
                         double lam, const Tv2VjpEpi &epi, hipStream_t s);
+
+// The pointwise kernels of that second route, generic in a: they serve the general-p derivative's epilogue route too (tvp_vjp.hip;
+// DESIGN.md 6j).  pi[i] = fma(g[i], scale, -zeta[i]) (TV2_VJP_PD's load) ; the write-out of epi.mode on a = J g, one element per thread ;
+// glam[j] += part[j].
+void fibre_vjp_cotangent(const Tv2VjpEpi &epi, const double *g, double *pi, long n, hipStream_t s);
+void fibre_vjp_write_out(const Tv2VjpEpi &epi, const double *a, const double *g, double *gx, long n, hipStream_t s);
+void fibre_vjp_glam_add(double *glam, const double *part, long count, hipStream_t s);
+
+// The epilogue route, whichever prox J belongs to: `plain(cot, a, glam)` enqueues a = J cot (and the per-fibre glam, where the pointer
+// is not null) by the plain call; around it the pre-pass of TV2_VJP_PD, the glam accumulation and the write-out of epi.mode.
+template <class Plain>
+void fibre_vjp_epilogue_route(const Tv2VjpEpi &epi, const double *g, double *gx, double *glam, long n, long fibres, hipStream_t s,
+                              const Plain &plain) {
+    const size_t bytes = sizeof(double) * (size_t)n;
+    Scratch a(bytes);
+    std::unique_ptr<Scratch> pi, part;
+    const double *cot = g;
+    if (epi.mode == TV2_VJP_PD) {
+        pi.reset(new Scratch(bytes));
+        fibre_vjp_cotangent(epi, g, pi->d(), n, s);
+        cot = pi->d();
+    }
+    const bool add = glam && epi.add_glam;
+    if (add) part.reset(new Scratch(sizeof(double) * (size_t)fibres));
+    plain(cot, a.d(), add ? part->d() : glam);
+    if (add) fibre_vjp_glam_add(glam, part->d(), fibres, s);
+    fibre_vjp_write_out(epi, a.d(), g, gx, n, s);
+}
 
 // ---- shared by the two units ----
 // whether fibres of this geometry go through the parallel-inside-the-fibre path (tv2_long_*) -- the forward and the derivative agree

@@ -126,6 +126,26 @@ bool tv2_vjp_direct(const FibreGeom &geo, double lam) { return !tv2_long_route(g
 
 }  // namespace
 
+void fibre_vjp_cotangent(const Tv2VjpEpi &epi, const double *g, double *pi, long n, hipStream_t s) {
+    hipLaunchKernelGGL(tv2_vjp_cotangent_kernel, dim3(pointwise_blocks(n)), dim3(256), 0, s, epi, g, pi, n);
+    PTV_HIP(hipGetLastError());
+}
+
+void fibre_vjp_glam_add(double *glam, const double *part, long count, hipStream_t s) {
+    hipLaunchKernelGGL(tv2_vjp_glam_add_kernel, dim3(pointwise_blocks(count)), dim3(256), 0, s, glam, part, count);
+    PTV_HIP(hipGetLastError());
+}
+
+void fibre_vjp_write_out(const Tv2VjpEpi &epi, const double *a, const double *g, double *gx, long n, hipStream_t s) {
+    switch (epi.mode) {
+        case TV2_VJP_DR_ROW: launch_epilogue<TV2_VJP_DR_ROW>(epi, a, g, gx, n, s); break;
+        case TV2_VJP_DR_COL: launch_epilogue<TV2_VJP_DR_COL>(epi, a, g, gx, n, s); break;
+        case TV2_VJP_PD2:    launch_epilogue<TV2_VJP_PD2>(epi, a, g, gx, n, s); break;
+        case TV2_VJP_PD:     launch_epilogue<TV2_VJP_PD>(epi, a, g, gx, n, s); break;
+        default:             launch_epilogue<TV2_VJP_PLAIN>(epi, a, g, gx, n, s); break;
+    }
+}
+
 void tv2_fibres_vjp(const double *y, const double *mu, const double *g, double *gx, double *glam, const int *ns, int nds, int dim,
                     double lam, hipStream_t s) {
     long n = 1;
@@ -176,28 +196,9 @@ void tv2_fibres_vjp_epi(const double *y, const double *mu, const double *g, doub
         return;
     }
     // a = J g (J pi) into scratch by the plain call, whichever route it takes; then the write-out, one element per thread
-    Scratch a(bytes);
-    std::unique_ptr<Scratch> pi, part;
-    const double *cot = g;
-    if (epi.mode == TV2_VJP_PD) {
-        pi.reset(new Scratch(bytes));
-        hipLaunchKernelGGL(tv2_vjp_cotangent_kernel, dim3(pointwise_blocks(n)), dim3(256), 0, s, epi, g, pi->d(), n);
-        PTV_HIP(hipGetLastError());
-        cot = pi->d();
-    }
-    const bool add = glam && epi.add_glam;
-    if (add) part.reset(new Scratch(sizeof(double) * (size_t)geo.count));
-    tv2_fibres_vjp(y, mu, cot, a.d(), add ? part->d() : glam, ns, nds, dim, lam, s);
-    if (add) {
-        hipLaunchKernelGGL(tv2_vjp_glam_add_kernel, dim3(pointwise_blocks(geo.count)), dim3(256), 0, s, glam, part->d(), geo.count);
-        PTV_HIP(hipGetLastError());
-    }
-    switch (epi.mode) {
-        case TV2_VJP_DR_ROW: launch_epilogue<TV2_VJP_DR_ROW>(epi, a.d(), g, gx, n, s); break;
-        case TV2_VJP_DR_COL: launch_epilogue<TV2_VJP_DR_COL>(epi, a.d(), g, gx, n, s); break;
-        case TV2_VJP_PD2:    launch_epilogue<TV2_VJP_PD2>(epi, a.d(), g, gx, n, s); break;
-        default:             launch_epilogue<TV2_VJP_PD>(epi, a.d(), g, gx, n, s); break;
-    }
+    fibre_vjp_epilogue_route(epi, g, gx, glam, n, geo.count, s, [&](const double *cot, double *a, double *gl) {
+        tv2_fibres_vjp(y, mu, cot, a, gl, ns, nds, dim, lam, s);
+    });
 }
 
 }  // namespace ptv

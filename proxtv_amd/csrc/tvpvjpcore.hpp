@@ -25,6 +25,11 @@
 // and the two z_i / d_i -- three arrays laid out like the data.  Samples are handled kBlock at a time so that the loads and the pow calls
 // of a block do not sit on the recurrence.  gx may be g: the elimination has read all of g before the substitution writes, and the dual's
 // substitution reads sample i of g just before it writes it.  Nothing depends on timing: the same call gives the same bits.
+//
+// solve() takes the load of the cotangent and the store of the result as functors (the contract of tv2vjp::fibre): `cot(i)`
+// is called wherever passes 1, 3 and (dual arm) 4 read g_i and must hand out the same bits every time; `put(i, a_i)` receives a = J g
+// in the order pass 4 produces it -- last sample first, sample 0 last -- each sample once, and after the last cot(i) of that sample, so
+// that it may rewrite the cotangent's own array.  With the defaults (F.g, F.gx) the arithmetic is what it was without them.
 #pragma once
 
 #include <cmath>
@@ -55,7 +60,8 @@ struct Fibre {
 };
 
 // p > 2: eliminates K = I + D' diag(c s^(p-2)) D on the right-hand sides g and b = D' phi; ba = b'K^-1 g, be = b'K^-1 b
-PTV_HD void eliminate_primal(const Fibre &F, double N, double c, double &ba, double &be) {
+template <class Cot>
+PTV_HD void eliminate_primal(const Fibre &F, const Cot &cot, double N, double c, double &ba, double &be) {
     const int n = F.n, nn = n - 1;
     const double pm2 = F.p - 2.0;
     double sa = 0.0, se = 0.0;
@@ -68,7 +74,7 @@ PTV_HD void eliminate_primal(const Fibre &F, double N, double c, double &ba, dou
             yy[k] = (i >= 0 && i < n) ? F.ld(F.y, i) : 0.0;
         }
 #pragma unroll
-        for (int k = 0; k < kBlock; k++) gg[k] = (i0 + k < n) ? F.ld(F.g, i0 + k) : 0.0;
+        for (int k = 0; k < kBlock; k++) gg[k] = (i0 + k < n) ? cot(i0 + k) : 0.0;
         double al[kBlock + 1], ph[kBlock + 1];   // edge i0 - 1 + k, between yy[k] and yy[k + 1]: c s^(p-2) and phi
 #pragma unroll
         for (int k = 0; k <= kBlock; k++) {
@@ -105,7 +111,8 @@ PTV_HD void eliminate_primal(const Fibre &F, double N, double c, double &ba, dou
 }
 
 // p > 2: gx = K^-1 (g + kappa b), last sample first
-PTV_HD void substitute_primal(const Fibre &F, double kappa) {
+template <class Put>
+PTV_HD void substitute_primal(const Fibre &F, const Put &put, double kappa) {
     double next = 0.0;
     for (int i1 = F.n - 1; i1 >= 0; i1 -= kBlock) {
         double ll[kBlock], zz[kBlock];
@@ -120,7 +127,7 @@ PTV_HD void substitute_primal(const Fibre &F, double kappa) {
             const int i = i1 - k;
             if (i >= 0) {
                 const double v = zz[k] - ll[k] * next;
-                F.st(F.gx, i, v);
+                put(i, v);
                 next = v;
             }
         }
@@ -128,7 +135,8 @@ PTV_HD void substitute_primal(const Fibre &F, double kappa) {
 }
 
 // p < 2: eliminates K = T + diag(cd s^(2-p)) on the right-hand sides h = D g and t = w / N; ta = t'K^-1 h, te = t'K^-1 t
-PTV_HD void eliminate_dual(const Fibre &F, double N, double cd, double &ta, double &te) {
+template <class Cot>
+PTV_HD void eliminate_dual(const Fibre &F, const Cot &cot, double N, double cd, double &ta, double &te) {
     const int n = F.n, nn = n - 1;
     const double tmp = 2.0 - F.p;
     double sa = 0.0, se = 0.0;
@@ -139,7 +147,7 @@ PTV_HD void eliminate_dual(const Fibre &F, double N, double cd, double &ta, doub
         for (int k = 0; k <= kBlock; k++) {
             const bool on = i0 + k < n;
             yy[k] = on ? F.ld(F.y, i0 + k) : 0.0;
-            gg[k] = on ? F.ld(F.g, i0 + k) : 0.0;
+            gg[k] = on ? cot(i0 + k) : 0.0;
         }
         double dg[kBlock], tt[kBlock];   // edge i0 + k: the diagonal of K and t
 #pragma unroll
@@ -176,7 +184,8 @@ PTV_HD void eliminate_dual(const Fibre &F, double N, double cd, double &ta, doub
 }
 
 // p < 2: v = K^-1 (h - kappa t), last edge first; gx_{i+1} = g_{i+1} - v_i + v_{i+1} as it goes, gx_0 = g_0 + v_0
-PTV_HD void substitute_dual(const Fibre &F, double kappa) {
+template <class Cot, class Put>
+PTV_HD void substitute_dual(const Fibre &F, const Cot &cot, const Put &put, double kappa) {
     const int nn = F.n - 1;
     double next = 0.0;   // v_{i+1} ; v_{n-1} = 0
     for (int i1 = nn - 1; i1 >= 0; i1 -= kBlock) {
@@ -186,26 +195,27 @@ PTV_HD void substitute_dual(const Fibre &F, double kappa) {
             const int i = i1 - k;
             ll[k] = (i >= 0) ? F.ld(F.ll, i) : 0.0;
             zz[k] = (i >= 0) ? F.ld(F.z1, i) - kappa * F.ld(F.z2, i) : 0.0;
-            gg[k] = (i >= 0) ? F.ld(F.g, i + 1) : 0.0;
+            gg[k] = (i >= 0) ? cot(i + 1) : 0.0;
         }
 #pragma unroll
         for (int k = 0; k < kBlock; k++) {
             const int i = i1 - k;
             if (i >= 0) {
                 const double v = zz[k] - ll[k] * next;
-                F.st(F.gx, i + 1, (gg[k] - v) + next);
+                put(i + 1, (gg[k] - v) + next);
                 next = v;
             }
         }
     }
-    F.st(F.gx, 0, F.ld(F.g, 0) + next);
+    put(0, cot(0) + next);
 }
 
-// One fibre: writes gx, returns glam.
-PTV_HD double solve(const Fibre &F) {
+// One fibre: hands a = J g to `put`, returns glam.
+template <class Cot, class Put>
+PTV_HD double solve(const Fibre &F, const Cot &cot, const Put &put) {
     const int n = F.n, nn = n - 1;
     if (nn <= 0 || !(F.lam > 0.0)) {   // the prox is the identity
-        for (int i = 0; i < n; i++) F.st(F.gx, i, F.ld(F.g, i));
+        for (int i = n - 1; i >= 0; i--) put(i, cot(i));
         return 0.0;
     }
     // pass 1: the largest jump of the output, the sum of the cotangent
@@ -215,7 +225,7 @@ PTV_HD double solve(const Fibre &F) {
 #pragma unroll
         for (int k = 0; k <= kBlock; k++) yy[k] = (i0 + k < n) ? F.ld(F.y, i0 + k) : 0.0;
 #pragma unroll
-        for (int k = 0; k < kBlock; k++) gg[k] = (i0 + k < n) ? F.ld(F.g, i0 + k) : 0.0;
+        for (int k = 0; k < kBlock; k++) gg[k] = (i0 + k < n) ? cot(i0 + k) : 0.0;
 #pragma unroll
         for (int k = 0; k < kBlock; k++) {
             if (i0 + k < n) gsum += gg[k];
@@ -227,7 +237,7 @@ PTV_HD double solve(const Fibre &F) {
     }
     if (!(wmax > 0.0)) {   // the forward answered with the mean
         const double mean = gsum / (double)n;
-        for (int i = 0; i < n; i++) F.st(F.gx, i, mean);
+        for (int i = n - 1; i >= 0; i--) put(i, mean);
         return 0.0;
     }
     // pass 2: N = ||w||_p in powers of |w_i| / max |w| (no power overflows)
@@ -245,17 +255,22 @@ PTV_HD double solve(const Fibre &F) {
     if (F.p > 2.0) {
         const double c = F.lam * (F.p - 1.0) / N;
         double ba, be;
-        eliminate_primal(F, N, c, ba, be);
+        eliminate_primal(F, cot, N, c, ba, be);
         const double kappa = c * ba / (1.0 - c * be);
-        substitute_primal(F, kappa);
+        substitute_primal(F, put, kappa);
         return -(ba + kappa * be);
     }
     const double cd = N / (F.lam * (F.p - 1.0));   // (q - 1) N / lambda
     double ta, te;
-    eliminate_dual(F, N, cd, ta, te);
+    eliminate_dual(F, cot, N, cd, ta, te);
     const double kappa = ta / te;
-    substitute_dual(F, kappa);
+    substitute_dual(F, cot, put, kappa);
     return -kappa;
+}
+
+// the plain call: the cotangent is F.g, the result goes to F.gx
+PTV_HD double solve(const Fibre &F) {
+    return solve(F, [&F](int i) { return F.ld(F.g, i); }, [&F](int i, double v) { F.st(F.gx, i, v); });
 }
 
 }  // namespace tvpvjp

@@ -27,7 +27,8 @@
 // All three loops take a norm in {1, 2} per direction / term (proxtv_DR2_TVp_vjp_dev, proxtv_PD_TVp_vjp_dev): every
 // reverse recurrence is linear in a = J g, whichever prox J belongs to.  A TV-L1 sweep keeps the launches described above; a TV-L2
 // sweep is tv2_fibres with its multipliers forward and tv2_vjp.hip's kernel with the same write-out mode in reverse (tape_prox /
-// tape_vjp), and SweepTape says what each keeps.
+// tape_vjp), and SweepTape says what each keeps.  With option general_p_vjp a norm may also be a general p: tvp_fibres
+// forward, tvp_vjp.hip's kernel in reverse, from the sweep's output alone.
 #include "solvers.hpp"
 #include "vjpcore.hpp"
 
@@ -39,6 +40,8 @@
 #include "pointwise.hpp"
 #include "sweep.hpp"
 #include "tv2.hpp"
+#include "tvp.hpp"
+#include "tvp_vjp.hpp"
 
 namespace ptv {
 
@@ -478,24 +481,29 @@ __global__ __launch_bounds__(256) void dr_vjp_mean_term_kernel(double *gU, long 
 //   TV-L1, tape = 0   K outputs                                          8 K n bytes
 //   TV-L1, tape = 1   one array the sweeps reuse, K word arrays          8 n + 4 K words
 //   TV-L2, any tape   K outputs and K multiplier arrays (one double per fibre): the derivative reads D y itself     8 K (n + fibres)
+//   TV-Lp, any tape   K outputs, nothing else: the derivative needs the output, lambda and p alone                   8 K n
 // Inside the one scratch block: every term's doubles, in the order of the terms, then every term's words.
 struct SweepTape {
-    bool l2 = false;
+    bool l2 = false, gen = false;   // TV-L2 ; a general p (neither: TV-L1)
+    double p = 1.0;
     int K = 0, tape = 0;
     size_t n = 0, fibres = 0, units = 0;   // samples ; fibres along the term's dimension ; step-code words of one output
     double *out = nullptr, *mus = nullptr;
     unsigned *words = nullptr;
-    size_t doubles() const { return l2 ? (size_t)K * (n + fibres) : (tape ? n : (size_t)K * n); }
-    size_t nwords() const { return (!l2 && tape) ? (size_t)K * units : 0; }
-    double *y(int k) const { return out + ((l2 || !tape) ? (size_t)k * n : 0); }
+    size_t doubles() const { return l2 ? (size_t)K * (n + fibres) : ((tape && !gen) ? n : (size_t)K * n); }
+    size_t nwords() const { return (!l2 && !gen && tape) ? (size_t)K * units : 0; }
+    double *y(int k) const { return out + ((l2 || gen || !tape) ? (size_t)k * n : 0); }
     double *mu(int k) const { return l2 ? mus + (size_t)k * fibres : nullptr; }
     unsigned *w(int k) const { return words ? words + (size_t)k * units : nullptr; }
+    bool per_fibre() const { return l2 || gen; }   // one penalty gradient per fibre (TV-L1: per edge)
 };
 
 SweepTape sweep_tape(const int *ns, int nds, int dim, double norm, int K, int tape) {
     SweepTape t;
     const FibreGeom geo = fibres_along(ns, nds, dim);
     t.l2 = norm == 2;
+    t.gen = norm != 1 && norm != 2;
+    t.p = norm;
     t.K = K;
     t.tape = tape;
     if (geo.count <= 0 || geo.len <= 0) return t;
@@ -530,8 +538,9 @@ void tape_carve(std::vector<SweepTape> &terms, double *block) {
 
 // sweep k of a term, forward: its output (and, TV-L2, its multipliers) where the tape keeps them
 void tape_prox(const double *in, const SweepTape &t, int k, const int *ns, int nds, int dim, double lam, const double *weights, hipStream_t s) {
-    if (t.l2) tv2_fibres(in, t.y(k), ns, nds, dim, lam, s, t.mu(k));
-    else      tv1_fibres(in, t.y(k), ns, nds, dim, lam, weights, s);
+    if (t.l2)       tv2_fibres(in, t.y(k), ns, nds, dim, lam, s, t.mu(k));
+    else if (t.gen) tvp_fibres(in, t.y(k), nullptr, ns, nds, dim, lam, t.p, s);
+    else            tv1_fibres(in, t.y(k), ns, nds, dim, lam, weights, s);
 }
 
 constexpr int tv2_mode_of(int mode) {
@@ -540,11 +549,11 @@ constexpr int tv2_mode_of(int mode) {
 }
 
 // ... and in reverse, a = J g with J that sweep's Jacobian and the write-out MODE: the segmented mean from the output or its words
-// (gw: per edge), or the TV-L2 derivative from the output and its multipliers (gw: per fibre)
+// (gw: per edge), the TV-L2 derivative from the output and its multipliers, or the general-p one from the output alone (gw: per fibre)
 template <int MODE>
 void tape_vjp(const SweepTape &t, int k, const double *g, double *gx, double *gw, const int *ns, int nds, int dim, double lam, const FibreGeom &geo,
               Summary *S, Resolved *R, const VjpEpi &epi, hipStream_t s) {
-    if (!t.l2) {
+    if (!t.per_fibre()) {
         vjp_launch_taped<MODE>(t.y(k), t.w(k), g, gx, gw, geo, S, R, epi, s);
         return;
     }
@@ -556,13 +565,14 @@ void tape_vjp(const SweepTape &t, int k, const double *g, double *gx, double *gw
     e.add_glam = epi.add_gw;
     e.zeta = epi.zeta;
     e.scale = epi.scale;
-    tv2_fibres_vjp_epi(t.y(k), t.mu(k), g, gx, gw, ns, nds, dim, lam, e, s);
+    if (t.l2) tv2_fibres_vjp_epi(t.y(k), t.mu(k), g, gx, gw, ns, nds, dim, lam, e, s);
+    else      tvp_fibres_vjp_epi(t.y(k), g, gx, gw, ns, nds, dim, lam, t.p, e, s);
 }
 
 }  // namespace
 
 // bytes = sum over the two directions d (n = M N B, K = maxit + 1):  TV-L1, tape 0: 8 K n ;  TV-L1, tape 1: 8 n + 4 K words_d ;
-// TV-L2: 8 K (n + fibres_d), fibres_0 = N B, fibres_1 = M B
+// TV-L2: 8 K (n + fibres_d), fibres_0 = N B, fibres_1 = M B ;  a general p: 8 K n
 size_t dr2_vjp_tape_bytes(size_t M, size_t N, size_t B, int maxit, int tape, double norm1, double norm2) {
     if (maxit <= 0) maxit = MAX_ITERS_DR;
     const int ns[3] = {(int)M, (int)N, (int)B};
@@ -582,7 +592,7 @@ size_t dr2_vjp_tape_bytes(size_t M, size_t N, size_t B, int maxit, int tape, dou
 void dr2_vjp(size_t M, size_t N, size_t B, const double *unary, double W1, double W2, const double *W1m, const double *W2m, const double *g,
              double *out, double *gU, double *gW1, double *gW2, double *glam, int maxit, int tape, hipStream_t s, double norm1, double norm2) {
     const long n1 = (long)(M * N), n = n1 * (long)B;
-    const bool l2c = norm1 == 2, l2r = norm2 == 2;   // (a TV-L2 direction: one uniform image, no per-edge gradients)
+    const bool l2c = norm1 != 1, l2r = norm2 != 1;   // (a TV-L2 or general-p direction: one uniform image, no per-edge gradients)
     if (l2c) gW1 = nullptr;
     if (l2r) gW2 = nullptr;
     if (maxit <= 0) maxit = MAX_ITERS_DR;
@@ -682,7 +692,7 @@ std::vector<SweepTape> pd_tapes(int which, const double *dims, const double *nor
 }  // namespace
 
 // bytes = sum over the terms i (n the array's size, K = iters, or 1 for which = 0 with one term):  TV-L1, tape 0: 8 K n ;
-// TV-L1, tape 1: 8 n + 4 K words_i ;  TV-L2: 8 K (n + fibres_i), fibres_i = n / ns[dims[i] - 1]
+// TV-L1, tape 1: 8 n + 4 K words_i ;  TV-L2: 8 K (n + fibres_i), fibres_i = n / ns[dims[i] - 1] ;  a general p: 8 K n
 size_t pd_vjp_tape_bytes(int which, const double *dims, const int *ns, int nds, int npen, int iters, int tape, const double *norms) {
     return tape_bytes(pd_tapes(which, dims, norms, ns, nds, npen, iters, tape));
 }
@@ -696,7 +706,7 @@ struct TermGw {
     double *d() const { return buf ? buf->d() : nullptr; }
 };
 void term_gw(TermGw &t, const FibreGeom &geo, bool wanted, bool l2 = false) {
-    t.edges = l2 ? geo.count : geo.count * (long)(geo.len - 1);   // (a TV-L2 sweep hands out one value per fibre)
+    t.edges = l2 ? geo.count : geo.count * (long)(geo.len - 1);   // (a TV-L2 or general-p sweep hands out one value per fibre)
     if (wanted && t.edges > 0) t.buf.reset(new Scratch(sizeof(double) * (size_t)t.edges));
 }
 // glam[i] = the sum of term i's per-edge gradients, in sum_to's fixed layout (0 where there are no edges)
@@ -733,8 +743,8 @@ void pd2_vjp(const double *y, const double *lambdas, const double *dims, const i
     tape_carve(kept_of, kept.d());
     const SweepTape &t0 = kept_of[0], &t1 = kept_of[npen >= 2 ? 1 : 0];
     std::vector<TermGw> gw((size_t)npen);
-    term_gw(gw[0], g0, glam != nullptr, t0.l2);
-    if (npen >= 2) term_gw(gw[1], g1, glam != nullptr, t1.l2);
+    term_gw(gw[0], g0, glam != nullptr, t0.per_fibre());
+    if (npen >= 2) term_gw(gw[1], g1, glam != nullptr, t1.per_fibre());
     const long units = std::max(vjp_units(g0), vjp_units(g1));
     Scratch S(sizeof(Summary) * (size_t)units), R(sizeof(Resolved) * (size_t)units);
     if (npen == 1) {   // (x + p stays y: every iteration repeats the first)
@@ -804,7 +814,7 @@ void pdp_vjp(const double *y, const double *lambdas, const double *dims, const i
     for (int i = 0; i < P; i++) {
         z.emplace_back(new Scratch(bytes));
         geo.push_back(fibres_along(ns, nds, (int)(dims[i] - 1)));
-        term_gw(gw[(size_t)i], geo.back(), glam != nullptr, kept_of[(size_t)i].l2);
+        term_gw(gw[(size_t)i], geo.back(), glam != nullptr, kept_of[(size_t)i].per_fibre());
         units = std::max(units, vjp_units(geo.back()));
         PTV_HIP(hipMemcpyAsync(z.back()->d(), y, bytes, hipMemcpyDeviceToDevice, s));
     }

@@ -137,14 +137,19 @@ def _norm_array(ps, count, what):
     return norms
 
 
-def _norms(ps, count, what="ps"):
-    """The norms of `count` terms as the derivative calls take them (float64, each 1 or 2, whatever option general_p says), or None for
-    ps = None."""
+def _norms(ps, count, what="ps", forward_too=False):
+    """The norms of `count` terms as the derivative calls take them (float64, each 1 or 2 whatever option general_p says; with option
+    general_p_vjp any 1.002 < p < 100), or None for ps = None.  `forward_too`: _lib.check_vjp_norms."""
     if ps is None:
         return None
     norms = _norm_array(ps, count, what)
     if not np.all((norms == 1) | (norms == 2)):
-        raise NotImplementedError(f"{what}: only p = 1 (TV-L1) and p = 2 (TV-L2) are implemented on the device, got {list(norms)}")
+        try:
+            _lib.check_vjp_norms(norms, forward_too)
+        except NotImplementedError as e:
+            if _lib.option_value("general_p_vjp") or (forward_too and _lib.option_value("general_p")):
+                raise NotImplementedError(f"{what}: {e}") from None
+            raise NotImplementedError(f"{what}: only p = 1 (TV-L1) and p = 2 (TV-L2) are implemented on the device, got {list(norms)}") from None
     return norms
 
 
@@ -397,13 +402,15 @@ def dr2_vjp(x, g, w_col, w_row=None, max_iters=0, weights_col=None, weights_row=
 
     p_col / p_row in {1, 2}: the derivative of ``tvp_2d(x, w_col, w_row, p_col, p_row)`` (proxtv_DR2_TVp_vjp_dev) -- one (M, N) image,
     uniform penalties only.  A TV-L2 direction has no per-edge gradient: gw_col / gw_row come back None and glam (`need_gw`) holds the
-    gradients in (w_col, w_row).  Its sweeps keep their float64 output and one multiplier per fibre under either tape."""
+    gradients in (w_col, w_row).  Its sweeps keep their float64 output and one multiplier per fibre under either tape.  With
+    proxtv_amd.general_p_vjp(True) a direction also takes any 1.002 < p < 100: the same conventions, its sweeps keep their
+    float64 output alone; the call replays the forward itself and does not ask for option general_p."""
     _check(x, "x")
     tape = _tape(tape)
     norms = _norms((p_col, p_row), 2, "p_col / p_row")
-    if np.any(norms == 2):
+    if np.any(norms != 1):
         if weights_col is not None or weights_row is not None:
-            raise ValueError("per-edge weight maps go with p = 1 only: TV-L2 has one penalty per fibre")
+            raise ValueError("per-edge weight maps go with p = 1 only: TV-L2 and TV-Lp have one penalty per fibre")
         return _dr2p_vjp(x, g, w_col, w_col if w_row is None else w_row, norms, max_iters, need_gw, need_y, tape)
     if x.dim() not in (2, 3):
         raise ValueError(f"x: expected an (M, N) image or an (M, N, B) batch, got {x.dim()} dimensions")
@@ -459,7 +466,7 @@ def _cotangent(g, x):
 
 def _dr2p_vjp(x, g, w_col, w_row, norms, max_iters, need_gw, need_y, tape):
     if x.dim() != 2:
-        raise ValueError(f"x: a TV-L2 direction takes one (M, N) image, got {x.dim()} dimensions")
+        raise ValueError(f"x: a TV-L2 or TV-Lp direction takes one (M, N) image, got {x.dim()} dimensions")
     g = _cotangent(g, x)
     M, N = x.shape
     gx = colmajor_empty(x.shape, device=x.device)
@@ -487,7 +494,8 @@ def tvgen_vjp(x, g, ws, ds, iters, method=None, need_glam=False, need_y=False, t
     and one array of x's size per term; every result is the same bits.  A `g` in another layout is copied.
 
     ps (one of {1, 2} per term, or None = all 1): the derivative of ``tvgen(x, ws, ds, method=method, ps=ps)``
-    (proxtv_PD_TVp_vjp_dev); a TV-L2 term's sweeps keep their float64 output and one multiplier per fibre under either tape."""
+    (proxtv_PD_TVp_vjp_dev); a TV-L2 term's sweeps keep their float64 output and one multiplier per fibre under either tape.  With
+    proxtv_amd.general_p_vjp(True) a term also takes any 1.002 < p < 100: its sweeps keep their float64 output alone."""
     _check(x, "x")
     tape = _tape(tape)
     if not (isinstance(g, torch.Tensor) and g.is_cuda and g.dtype == torch.float64):
