@@ -210,7 +210,9 @@ int proxtv_set_option(const char *key, int value);
                     calls replay the forward themselves: general_p is not asked.  With 1 and every norm in {1, 2} they run the launches
                     and return the bits of 0.
      tvp_vjp_route  debugging aid: where the write-out of a general-p reverse sweep runs -- 0 (default) by the fibre count, 1 inside the
-                    fibre kernel wherever legal, 2 as a pointwise pass behind the plain kernel everywhere.  The same bits all three. */
+                    fibre kernel wherever legal, 2 as a pointwise pass behind the plain kernel everywhere.  The same bits all three.
+     dr_jvp_route   debugging aid: where proxtv_DR2_TV_jvp_dev forms the three-array tangent of a row sweep -- 0 (default) the measured
+                    choice, 1 inside the loads of the sweep's two passes, 2 as one pointwise pass in front.  The same bits all three. */
 
 /* Device-pointer solvers: every double* is an HBM pointer valid on the current device, `stream` is
    a hipStream_t (NULL = the library's per-thread stream), `info` is a HOST double[3] or NULL.
@@ -294,6 +296,40 @@ int proxtv_tv1_fibres_vjp_dev(const double *y, const double *g, double *gx /*or 
 int proxtv_DR2_TV_vjp_dev(size_t M, size_t N, size_t B, const double *unary, double W1, double W2, const double *W1m /*or NULL*/,
                           const double *W2m /*or NULL*/, const double *g, double *s /*or NULL*/, double *gU, double *gW1 /*or NULL*/,
                           double *gW2 /*or NULL*/, double *glam /*host, or NULL*/, int maxit, void *stream);
+
+/* Forward mode.  The tangent of proxtv_tv1_fibres_dev at its output y, for tangents dx of the input and dr of the per-edge
+   penalties.  With sigma_k = +1 / -1 on a step up / down of y and 0 on an edge that is none (the rule above),
+     E[i] = sigma_i dr_i - sigma_{i-1} dr_{i-1}     (sample i of a fibre; an edge outside the fibre contributes 0)
+     dy   = P (dx + E)                              (shape of y; dy may be dx itself)
+   where dr_k = dw[k] + dlam: dw (or NULL: zero) has the shape and layout of gw above, dlam is the tangent of a uniform lambda.  dx NULL:
+   zero.  This is the exact transpose of proxtv_tv1_fibres_vjp_dev: <g, dy> = <gx, dx> + <gw, dr> for every g.  The limits are that
+   call's (kinks; the absolute 4e-10).  ns[dim] == 1: dy = dx.  Every tangent absent or zero: dy is exactly zero.  No array may overlap
+   another, except dy == dx; an overlap, a missing y / dy or a dimension out of range: returns 0 with proxtv_last_error set and nothing
+   written.  A total size of 0: returns 1.  No atomics: the same call gives the same bits.  Synchronises the stream; returns 1 on success. */
+int proxtv_tv1_fibres_jvp_dev(const double *y, const double *dx /*or NULL: zero*/, const double *dw /*per-edge, shape of gw, or NULL*/,
+                              double dlam /*uniform tangent, added on every edge*/, double *dy /*may be dx*/, const int *ns /*host*/,
+                              int nds, int dim, void *stream);
+
+/* The tangent of the 2-D Douglas-Rachford solves (DR2_TV / DR2L1W_TV / the batch), on B images stored back to back, for tangents
+     dU          of `unary`, or NULL (zero)                                 (M x N per image)
+     dW1m, dW2m  of the per-edge penalties, or NULL (zero), each on its own ((M-1) x N and M x (N-1) per image; also with uniform W1 / W2)
+     dW1, dW2    of uniform penalties, added on every edge of their direction
+     ds          the tangent of the result                                  (M x N per image)
+     s           the forward result, or NULL
+   W1m / W2m as for proxtv_DR2_TV_vjp_dev: both (the weighted solve) or neither.  The call differentiates the UNFUSED recurrence that
+   proxtv_DR2_TV_vjp_dev replays, sweep by sweep next to the forward: dt = 2 mean(dU); dx1 = P_c(x1)[dt + E(dW1)],
+   dx2 = P_r(x2)[dU - dt + 2 dx1 + E(dW2)], dt <- dt - dx1 + dx2; a final pair, ds = P_r(x2)[dU - dt + dx1 + E(dW2)].  Nothing is kept
+   between iterations but t and dt: the scratch is six arrays of the data's size plus 4 bytes a sample of chunk records, whatever maxit
+   (beyond the pool's cap, PROXTV_POOL_CAP_MB, the call is refused and proxtv_last_error names the bytes).  <g, ds> equals
+   <gU, dU> + <gW1, dW1m + dW1> + <gW2, dW2m + dW2> of proxtv_DR2_TV_vjp_dev up to rounding, and s is that call's s bit for bit.  Limits:
+   those of proxtv_DR2_TV_vjp_dev.  maxit <= 0: 35.  M*N*B == 0: returns 1, nothing is written.  M == 1 or N == 1 is fine.  Every tangent
+   absent or zero: ds is exactly zero.  Exactly one weight map, a missing unary / ds, any overlap: returns 0 with proxtv_last_error set and
+   nothing written.  No atomics: the same call gives the same bits, and an image of a batch the bits of its own call.  Synchronises the
+   stream; returns 1 on success. */
+int proxtv_DR2_TV_jvp_dev(size_t M, size_t N, size_t B, const double *unary, double W1, double W2, const double *W1m /*or NULL*/,
+                          const double *W2m /*or NULL*/, const double *dU /*or NULL*/, const double *dW1m /*or NULL*/,
+                          const double *dW2m /*or NULL*/, double dW1, double dW2, double *s /*forward result, or NULL*/, double *ds,
+                          int maxit, void *stream);
 
 /* The derivative of the two Dykstra loops tvgen dispatches to, with TV-L1 terms on an N-D array: which = 0, proxtv_PD2_TV_dev (one or two
    terms); which = 1, proxtv_PD_TV_dev (any number of terms, several may share a dimension).  For the cotangent g of the result,

@@ -76,6 +76,9 @@ SIGNATURES = {
     "proxtv_tv1_fibres_vjp_dev": (C.c_int, [_dp, _dp, _dp, _dp, _ip, _ip, C.c_int, C.c_int, C.c_void_p]),
     "proxtv_DR2_TV_vjp_dev": (C.c_int, [C.c_size_t, C.c_size_t, C.c_size_t, _dp, C.c_double, C.c_double, _dp, _dp, _dp, _dp, _dp, _dp, _dp,
                                         _dp, C.c_int, C.c_void_p]),
+    "proxtv_tv1_fibres_jvp_dev": (C.c_int, [_dp, _dp, _dp, C.c_double, _dp, _ip, C.c_int, C.c_int, C.c_void_p]),
+    "proxtv_DR2_TV_jvp_dev": (C.c_int, [C.c_size_t, C.c_size_t, C.c_size_t, _dp, C.c_double, C.c_double, _dp, _dp, _dp, _dp, _dp,
+                                        C.c_double, C.c_double, _dp, _dp, C.c_int, C.c_void_p]),
     "proxtv_PD_TV_vjp_dev": (C.c_int, [C.c_int, _dp, _dp, _dp, _ip, C.c_int, C.c_int, C.c_int, _dp, _dp, _dp, _dp, C.c_void_p]),
     "proxtv_tv1_steps_words": (C.c_long, [_ip, C.c_int, C.c_int]),
     "proxtv_tv1_fibres_steps_dev": (C.c_int, [_dp, C.c_void_p, _ip, C.c_int, C.c_int, C.c_void_p]),

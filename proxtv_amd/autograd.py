@@ -27,6 +27,11 @@ as backward, from the saved output alone; a general p inside tvp_
 Every function takes ``tape="outputs"`` (the default) or ``tape="steps"``: what is kept for the reverse sweeps.  With "steps",
 tv1_fibres saves the 2-bit step codes of its output (device.tv1_fibres_steps: an int32 tensor of 1/32 of y's bytes) in the graph instead
 of y, and the solver derivatives keep step codes instead of their sweep outputs while they run.  Every gradient is the same bits.
+
+Forward mode: tv1_fibres, tv1_2d, tv1w_2d and tv1_2d_batch also work under ``torch.autograd.forward_ad.dual_level()``.  A
+dual x, a dual 0-d float64 w (its tangent is the d lambda of a uniform penalty) or dual weight maps give a dual result whose primal is the
+same fused solve and whose tangent is ONE device.tv1_fibres_jvp / device.dr2_jvp call: nothing is taped, so the scratch does not grow
+with max_iters.  torch.func transforms and vmap are not covered; the other functions of this module have no forward mode.
 """
 import torch
 
@@ -35,9 +40,11 @@ from . import device
 
 class _TV1Fibres(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, x, w, weights, dim, tape):
+    def forward(ctx, x, w, weights, dim, tape, dual):
         y = device.tv1_fibres(_colmajor(x.detach()), float(w), dim, None if weights is None else _colmajor(weights.detach()))
         ctx.save_for_backward(device.tv1_fibres_steps(y, dim) if tape == "steps" else y)
+        if dual:      # (forward mode reads the output itself, whatever the tape)
+            ctx.save_for_forward(y)
         ctx.dim, ctx.tape, ctx.shape = dim, tape, tuple(y.shape)
         ctx.w_device = w.device if isinstance(w, torch.Tensor) else None
         ctx.weighted = weights is not None
@@ -56,7 +63,14 @@ class _TV1Fibres(torch.autograd.Function):
         if need_w:
             # (with per-edge weights the scalar w does not enter the prox: its gradient is zero)
             gw_scalar = (torch.zeros((), dtype=torch.float64) if ctx.weighted else gw.sum()).to(ctx.w_device)
-        return (gx if need_x else None), gw_scalar, (gw if need_weights else None), None, None
+        return (gx if need_x else None), gw_scalar, (gw if need_weights else None), None, None, None
+
+    @staticmethod
+    def jvp(ctx, dx, dw, dweights, *_):
+        (y,) = ctx.saved_tensors
+        # (with per-edge weights the scalar w does not enter the prox: its tangent goes nowhere)
+        dlam = 0.0 if dw is None or ctx.weighted else float(dw)
+        return device.tv1_fibres_jvp(y, dx, ctx.dim, dweights=dweights if ctx.weighted else None, dw=dlam)
 
 
 def _colmajor(t):
@@ -70,9 +84,10 @@ def tv1_fibres(x, w, dim, weights=None, tape="outputs"):
         raise ValueError("w: expected a float or a 0-d float64 tensor")
     device._tape(tape)
     wants = torch.is_grad_enabled() and any(isinstance(t, torch.Tensor) and t.requires_grad for t in (x, w, weights))
-    if not wants:
+    dual = _dual(x, w, weights)
+    if not wants and not dual:
         return device.tv1_fibres(x, float(w), dim, weights)
-    return _TV1Fibres.apply(x, w, weights, int(dim), tape)
+    return _TV1Fibres.apply(x, w, weights, int(dim), tape, dual)
 
 
 class _TV2Fibres(torch.autograd.Function):
@@ -146,18 +161,22 @@ class _DR2(torch.autograd.Function):
     """x, then the two penalties: 0-d tensors / floats (uniform) or the two per-edge maps (`weighted`)."""
 
     @staticmethod
-    def forward(ctx, x, p_col, p_row, max_iters, weighted, tape):
+    def forward(ctx, x, p_col, p_row, max_iters, weighted, tape, dual):
         xd = _colmajor(x.detach())
         if weighted:
             wc, wr = _colmajor(p_col.detach()), _colmajor(p_row.detach())
             y, _ = device.tv1w_2d(xd, wc, wr, max_iters)
             ctx.save_for_backward(xd, wc, wr)
+            if dual:
+                ctx.save_for_forward(xd, wc, wr)
         else:
             if xd.dim() == 3:
                 y, _ = device.tv1_2d_batch(xd, float(p_col), max_iters)
             else:
                 y, _ = device.tv1_2d(xd, float(p_col), max_iters, w_row=float(p_row))
             ctx.save_for_backward(xd)
+            if dual:
+                ctx.save_for_forward(xd)
             ctx.lams = (float(p_col), float(p_row))
             ctx.lam_devices = tuple(p.device if isinstance(p, torch.Tensor) else None for p in (p_col, p_row))
         ctx.max_iters, ctx.weighted, ctx.tape = max_iters, weighted, tape
@@ -179,7 +198,17 @@ class _DR2(torch.autograd.Function):
             if glam is not None:
                 glam = glam.reshape(-1, 2).sum(axis=0)     # (a batch shares its penalties)
                 gc, gr = (None if d is None else torch.tensor(v, dtype=torch.float64, device=d) for v, d in zip(glam, ctx.lam_devices))
-        return (gx if need_x else None), (gc if need_col else None), (gr if need_row else None), None, None, None
+        return (gx if need_x else None), (gc if need_col else None), (gr if need_row else None), None, None, None, None
+
+    @staticmethod
+    def jvp(ctx, dx, d_col, d_row, *_):
+        if ctx.weighted:
+            x, wc, wr = ctx.saved_tensors
+            return device.dr2_jvp(x, dx, 0.0, max_iters=ctx.max_iters, weights_col=wc, weights_row=wr, dweights_col=d_col,
+                                  dweights_row=d_row)[0]
+        (x,) = ctx.saved_tensors
+        return device.dr2_jvp(x, dx, ctx.lams[0], ctx.lams[1], ctx.max_iters, dw_col=0.0 if d_col is None else float(d_col),
+                              dw_row=0.0 if d_row is None else float(d_row))[0]
 
 
 def _scalar_penalty(w, name):
@@ -191,6 +220,11 @@ def _wants(*ts):
     return torch.is_grad_enabled() and any(isinstance(t, torch.Tensor) and t.requires_grad for t in ts)
 
 
+def _dual(*ts):
+    """Whether any of the tensors carries a forward-mode tangent (torch.autograd.forward_ad)."""
+    return any(isinstance(t, torch.Tensor) and torch.autograd.forward_ad.unpack_dual(t).tangent is not None for t in ts)
+
+
 def tv1_2d(x, w, max_iters=0, w_row=None, tape="outputs"):
     """``device.tv1_2d(x, w, max_iters, w_row=w_row)[0]`` (the Douglas-Rachford solve) with a graph behind it: differentiable in x and in
     w / w_row where they are 0-d float64 tensors (the gradient comes back on that tensor's device; one tensor for both directions
@@ -198,17 +232,19 @@ def tv1_2d(x, w, max_iters=0, w_row=None, tape="outputs"):
     _scalar_penalty(w, "w")
     _scalar_penalty(w_row, "w_row")
     device._tape(tape)
-    if not _wants(x, w, w_row):
+    dual = _dual(x, w, w_row)
+    if not _wants(x, w, w_row) and not dual:
         return device.tv1_2d(x, float(w), max_iters, w_row=None if w_row is None else float(w_row))[0]
-    return _DR2.apply(x, w, w if w_row is None else w_row, int(max_iters), False, tape)
+    return _DR2.apply(x, w, w if w_row is None else w_row, int(max_iters), False, tape, dual)
 
 
 def tv1w_2d(x, w_col, w_row, max_iters=0, tape="outputs"):
     """``device.tv1w_2d(x, w_col, w_row, max_iters)[0]`` with a graph behind it: differentiable in x and in both weight maps."""
     device._tape(tape)
-    if not _wants(x, w_col, w_row):
+    dual = _dual(x, w_col, w_row)
+    if not _wants(x, w_col, w_row) and not dual:
         return device.tv1w_2d(x, w_col, w_row, max_iters)[0]
-    return _DR2.apply(x, w_col, w_row, int(max_iters), True, tape)
+    return _DR2.apply(x, w_col, w_row, int(max_iters), True, tape, dual)
 
 
 def tv1_2d_batch(xs, w, max_iters=0, tape="outputs"):
@@ -216,9 +252,10 @@ def tv1_2d_batch(xs, w, max_iters=0, tape="outputs"):
     float64 tensor w (the sum over the images and both directions)."""
     _scalar_penalty(w, "w")
     device._tape(tape)
-    if not _wants(xs, w):
+    dual = _dual(xs, w)
+    if not _wants(xs, w) and not dual:
         return device.tv1_2d_batch(xs, float(w), max_iters)[0]
-    return _DR2.apply(xs, w, w, int(max_iters), False, tape)
+    return _DR2.apply(xs, w, w, int(max_iters), False, tape, dual)
 
 
 class _DR2p(torch.autograd.Function):

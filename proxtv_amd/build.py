@@ -31,7 +31,7 @@ SWEEP_UNITS = [("OP_PROX", False), ("OP_PROX", True), ("OP_DR_COL", False), ("OP
                ("OP_DR_COL_FINAL", True), ("OP_DR_ROW", False), ("OP_DR_ROW", True), ("OP_DR_ROW_FINAL", False),
                ("OP_DRW_ROW_FINAL", True), ("OP_PD2_A", False), ("OP_PD2_B", False), ("OP_YANG", False), ("OP_DR_COL_V", False),
                ("OP_DR_COL_V", True), ("OP_DR_ROW_V", False), ("OP_DR_ROW_V", True)]
-PLAIN_UNITS = ["common", "sweep", "pin", "pinlong", "pointwise", "tv2", "tv2_vjp", "tvp", "tvp_vjp", "vjp", "solvers", "cabi"]
+PLAIN_UNITS = ["common", "sweep", "pin", "pinlong", "pointwise", "tv2", "tv2_vjp", "tvp", "tvp_vjp", "vjp", "jvp", "solvers", "cabi"]
 
 
 def units():

@@ -10,6 +10,7 @@
 #include <vector>
 
 #include "solvers.hpp"
+#include "jvp.hpp"
 #include "pointwise.hpp"
 #include "sweep.hpp"
 #include "tv2.hpp"
@@ -847,6 +848,65 @@ int proxtv_DR2_TV_vjp_tape_dev(size_t M, size_t N, size_t B, const double *unary
                                const double *g, double *s, double *gU, double *gW1, double *gW2, double *glam, int maxit, int tape,
                                void *stream) {
     return dr2_vjp_entry("proxtv_DR2_TV_vjp_tape_dev", M, N, B, unary, W1, W2, W1m, W2m, g, s, gU, gW1, gW2, glam, maxit, tape, stream);
+}
+
+// the forward-mode calls (jvp.hip): no array may overlap another -- `same` names the one pair that may coincide exactly (or null)
+namespace {
+struct JvpSpan { const double *p; size_t n; bool out; const char *name; };
+void check_jvp_spans(const JvpSpan *spans, size_t count, const JvpSpan *same_out, const JvpSpan *same_in, const char *rule) {
+    for (size_t a = 0; a < count; a++) {
+        const JvpSpan &o = spans[a];
+        if (!o.out || !o.p || !o.n) continue;
+        for (size_t b = 0; b < count; b++) {
+            const JvpSpan &i = spans[b];
+            if (&i == &o || !i.p || !i.n || (&o == same_out && &i == same_in && o.p == i.p)) continue;
+            if (i.out && &i > &o) continue;   // (a pair of outputs: once)
+            if (i.p < o.p + o.n && o.p < i.p + i.n) {
+                set_error("%s overlaps %s (%s)", o.name, i.name, rule);
+                throw HipFailure{hipErrorInvalidValue};
+            }
+        }
+    }
+}
+}  // namespace
+
+int proxtv_tv1_fibres_jvp_dev(const double *y, const double *dx, const double *dw, double dlam, double *dy, const int *ns, int nds, int dim,
+                              void *stream) {
+    return guarded("proxtv_tv1_fibres_jvp_dev", nullptr, 1, [&] {
+        if (dim < 0 || dim >= nds) reject("dimension out of range");
+        const size_t n = (size_t)total(ns, nds);
+        if (n == 0) return;
+        if (!y || !dy) reject("y and dy are required");
+        const size_t nw = ns[dim] > 1 ? n / (size_t)ns[dim] * (size_t)(ns[dim] - 1) : 0;
+        const JvpSpan spans[] = {{y, n, false, "y"}, {dx, n, false, "dx"}, {dw, nw, false, "dw"}, {dy, n, true, "dy"}};
+        check_jvp_spans(spans, 4, &spans[3], &spans[1], "only dy may alias dx, and then exactly");
+        tv1_fibres_jvp(y, dx, nw ? dw : nullptr, dlam, dy, ns, nds, dim, pick(stream));
+    });
+}
+
+int proxtv_DR2_TV_jvp_dev(size_t M, size_t N, size_t B, const double *unary, double W1, double W2, const double *W1m, const double *W2m,
+                          const double *dU, const double *dW1m, const double *dW2m, double dW1, double dW2, double *s, double *ds, int maxit,
+                          void *stream) {
+    return guarded("proxtv_DR2_TV_jvp_dev", nullptr, 1, [&] {
+        const size_t n = M * N * B;
+        if (n == 0) return;
+        if (M > 0x7fffffffu || N > 0x7fffffffu || B > 65535u) reject("image extents beyond 2^31 - 1 or more than 65535 images");
+        if (!unary || !ds) reject("unary and ds are required");
+        if ((W1m != nullptr) != (W2m != nullptr)) reject("weight maps come in pairs: W1m and W2m, or neither");
+        const size_t nw1 = (M - 1) * N * B, nw2 = M * (N - 1) * B;
+        const JvpSpan spans[] = {{unary, n, false, "unary"}, {W1m, nw1, false, "W1m"}, {W2m, nw2, false, "W2m"}, {dU, n, false, "dU"},
+                                 {dW1m, nw1, false, "dW1m"}, {dW2m, nw2, false, "dW2m"}, {s, n, true, "s"}, {ds, n, true, "ds"}};
+        check_jvp_spans(spans, 8, nullptr, nullptr, "no array of this call may alias another");
+        const size_t need = dr2_jvp_scratch_bytes(M, N, B);
+        if (need > pool_cap_bytes()) {
+            set_error("the call needs %zu bytes of scratch, the scratch pool is capped at %zu (PROXTV_POOL_CAP_MB)", need, pool_cap_bytes());
+            throw HipFailure{hipErrorOutOfMemory};
+        }
+        hipStream_t st = pick(stream);
+        SolveScope scope(st);
+        dr2_jvp(M, N, B, unary, W1, W2, W1m, W2m, dU, nw1 ? dW1m : nullptr, nw2 ? dW2m : nullptr, dW1, dW2, s, ds, maxit, st);
+        scope.finish();
+    });
 }
 
 // proxtv_PD_TV_vjp_dev is the tape = 0 call of proxtv_PD_TV_vjp_tape_dev

@@ -49,6 +49,7 @@ constexpr OptionEntry kOptionTable[] = {
     {"general_p", &Options::general_p},
     {"general_p_vjp", &Options::general_p_vjp},
     {"tvp_vjp_route", &Options::tvp_vjp_route},
+    {"dr_jvp_route", &Options::dr_jvp_route},
     {"ablate", &Options::ablate},
     {"debug_legacy_rebuild", &Options::debug_legacy_rebuild},
 };

@@ -74,6 +74,8 @@ struct Options {
                               // differentiate its sweeps with tvp_vjp.hip; 0 (default): they refuse every p outside {1, 2}, as they always have
     int tvp_vjp_route = 0;    // debugging aid: the write-out of a general-p reverse sweep -- 0 = by the fibre count (policy.hpp), 1 = inside the
                               // fibre kernel wherever legal, 2 = a pointwise pass behind the plain kernel everywhere; the same bits all three
+    int dr_jvp_route = 0;     // debugging aid: the three-array tangent of a Douglas-Rachford row sweep in forward mode (jvp.hip) -- 0 = policy.hpp's
+                              // choice, 1 = formed inside the loads of phases A and C, 2 = one pointwise pass in front; the same bits all three
     int debug_legacy_rebuild = 0;   // test aid: the along-fibre kernel's rebuild with the semantics of rounds 1-4 (an unproven chunk values its first
                                     // piece from its own first row) -- results MAY BE WRONG; exists so that the suite can watch `certify` catch it
 };

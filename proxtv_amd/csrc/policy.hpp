@@ -58,6 +58,13 @@ constexpr int kQuietSolves = 16;    // one-sweep solves between explorations
 constexpr long kTvpVjpFusedMinFibres = -1;   // fused from this many fibres on; negative: at no count
 inline bool tvp_vjp_fused_auto(long fibres) { return kTvpVjpFusedMinFibres >= 0 && fibres >= kTvpVjpFusedMinFibres; }
 
+// The tangent entering a row sweep of the forward-mode Douglas-Rachford derivative (jvp.hip) is dU - dt + 2 dx1: formed
+// inside the loads of phases A and C (both then read three arrays) or by one pointwise pass into a free array (the phases read one).
+// Decided by paired timing of whole 35-iteration calls, the routes taking turns (profiles/dr_jvp_time.txt): inside the
+// loads is slower by 0.36 ms of 8.0 at 1024^2 and by 2.44 ms of 51.1 at 4096^2 (medians of 20 pairs, both quartiles positive), so the
+// pointwise pass is the default; option dr_jvp_route runs either.
+constexpr bool kDrJvpCombineInLoads = false;
+
 // Seeding.  Before a solve the input's edges |y_k - y_{k-1}| are sampled along every dimension it sweeps (pointwise.hip's
 // edge_histogram); the fraction f of them above 4 lambda -- the edges at which the string is KNOWN to bend
 // (chunkcore.hpp) -- says which rung the data want: on unit noise f = 0.78 / 0.40 / 0.16 / 0.05 / 0.005 at lambda = 0.1 /

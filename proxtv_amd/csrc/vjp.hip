@@ -31,6 +31,7 @@
 // forward, tvp_vjp.hip's kernel in reverse, from the sweep's output alone.
 #include "solvers.hpp"
 #include "vjpcore.hpp"
+#include "jvp.hpp"
 
 #include <algorithm>
 #include <memory>
@@ -55,6 +56,7 @@ using vjp::Summary;
 constexpr int kVjpL = 16;             // samples per chunk: sixteen cotangents in registers per lane
 constexpr int kVjpRow = kVjpL + 1;    // LDS row of the contiguous kernel: the chunk plus the next sample's y; odd, so conflict-free
 static_assert((kVjpL & (kVjpL - 1)) == 0, "the staging loops split an element index by shifts");
+static_assert(kVjpL == kVjpChunk, "jvp.hip lays out its records for the same chunks (jvp.hpp)");
 
 // What a launch of the chunk kernels does: phase A, or phase C with one of three write-outs of the means a = P g.
 //   VJP_PLAIN    gx = a                                                    (proxtv_tv1_fibres_vjp_dev)
@@ -423,6 +425,14 @@ void vjp_encode(const double *y, unsigned *W, const FibreGeom &geo, hipStream_t 
 }
 
 }  // namespace
+
+// phase B alone, for the forward-mode kernels of jvp.hip: the launches vjp_launch makes between its phases A and C
+void vjp_resolve(vjp::Summary *S, vjp::Resolved *R, const FibreGeom &geo, int *nseg, hipStream_t s) {
+    const int nch = (geo.len + kVjpL - 1) / kVjpL;
+    if (geo.inc == 1) hipLaunchKernelGGL(vjp_resolve_contig_kernel, dim3((unsigned)((geo.count + 3) / 4)), dim3(256), 0, s, S, R, nch, geo.count, nseg);
+    else              hipLaunchKernelGGL(vjp_resolve_strided_kernel, dim3((unsigned)((geo.count + 63) / 64)), dim3(64), 0, s, S, R, nch, geo.count, nseg);
+    PTV_HIP(hipGetLastError());
+}
 
 void tv1_fibres_vjp(const double *y, const double *g, double *gx, double *gw, int *nseg, const int *ns, int nds, int dim, hipStream_t s) {
     const FibreGeom geo = fibres_along(ns, nds, dim);

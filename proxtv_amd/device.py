@@ -454,6 +454,88 @@ def dr2_vjp(x, g, w_col, w_row=None, max_iters=0, weights_col=None, weights_row=
     return gx, gw_col, gw_row, glam, y
 
 
+def _tangent(t, name, like, shape):
+    """A tangent array for the forward-mode calls: None stays None (zero); a float64 CUDA tensor of `shape` on like's device, copied
+    into column-major storage when it has another layout."""
+    if t is None:
+        return None
+    if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.float64):
+        raise ValueError(f"{name}: expected a float64 CUDA tensor")
+    if t.device != like.device:
+        raise ValueError(f"{name}: lives on {t.device}, the input on {like.device}")
+    if tuple(t.shape) != tuple(shape):
+        raise ValueError(f"{name}: shape {tuple(t.shape)}, expected {tuple(shape)}")
+    return t if _is_colmajor(t) else to_colmajor(t)
+
+
+def tv1_fibres_jvp(y, dx, dim, dweights=None, dw=0.0, out=None):
+    """The forward-mode derivative of ``y = tv1_fibres(x, w, dim[, weights])``: the tangent dy of `y` for the tangents `dx` of x (None:
+    zero), `dweights` of the per-edge penalties (shaped like `weights`, None: zero) and the float `dw` of a uniform penalty, which is
+    added on every edge.
+
+    dy = P (dx + E), where P replaces every sample by the mean over its segment of `y` and E[i] = sigma_i dr_i - sigma_{i-1} dr_{i-1}
+    with dr = dweights + dw and sigma = +1 / -1 / 0 on a step up / a step down / an edge that is no step (rule and limits:
+    include/proxtv_amd.h).  It is the exact transpose of tv1_fibres_vjp.  Only `y` is needed, neither x nor the penalties.  Tangents in
+    another layout are copied; `out` may be `dx`.  One call: proxtv_tv1_fibres_jvp_dev."""
+    _check(y, "y")
+    if not 0 <= int(dim) < y.dim():
+        raise ValueError(f"dim {dim} out of range for a {y.dim()}-D array")
+    dim = int(dim)
+    wshape = list(y.shape)
+    wshape[dim] = max(wshape[dim] - 1, 0)
+    dx = _tangent(dx, "dx", y, y.shape)
+    dweights = _tangent(dweights, "dweights", y, wshape)
+    dy = _out(out, y)
+    ns = np.array(y.shape, dtype=np.int32)
+    ptr = lambda t: t.data_ptr() if t is not None and t.numel() else 0   # noqa: E731
+    with torch.cuda.device(y.device):
+        lib = _lib.require_device()
+        lib.proxtv_tv1_fibres_jvp_dev(ptr(y), ptr(dx), ptr(dweights), float(dw), ptr(dy), ns.ctypes.data, y.dim(), dim, _stream(y.device))
+    _lib.check("device.tv1_fibres_jvp")
+    return dy
+
+
+def dr2_jvp(x, dx, w_col, w_row=None, max_iters=0, weights_col=None, weights_row=None, dw_col=0.0, dw_row=0.0, dweights_col=None,
+            dweights_row=None, need_y=False):
+    """The forward-mode derivative of the Douglas-Rachford solves ``tv1_2d(x, w_col, w_row=w_row)`` / ``tv1w_2d(x, weights_col,
+    weights_row)`` / ``tv1_2d_batch``: returns (dy, y), the tangent of their result for the tangents `dx` of x (None: zero), the floats
+    `dw_col` / `dw_row` of uniform penalties and `dweights_col` / `dweights_row` of the per-edge penalties (the shapes of `weights_col` /
+    `weights_row`, None: zero; a uniform and a per-edge tangent of one direction add up).
+
+    `x` is (M, N), or (M, N, B) for a batch of independent images.  y (`need_y`) is the forward result of the call's own, unfused
+    recurrence -- the bits of ``dr2_vjp(..., need_y=True)``, device.tv1_2d's up to rounding.  One call: proxtv_DR2_TV_jvp_dev
+    (include/proxtv_amd.h), which forms the tangent of every sweep next to the sweep and keeps nothing between iterations: its scratch is
+    six arrays of x's size whatever `max_iters`, where dr2_vjp keeps 2 (max_iters + 1).  Tangents in another layout are copied."""
+    _check(x, "x")
+    if x.dim() not in (2, 3):
+        raise ValueError(f"x: expected an (M, N) image or an (M, N, B) batch, got {x.dim()} dimensions")
+    if (weights_col is None) != (weights_row is None):
+        raise ValueError("weights_col and weights_row come in pairs")
+    M, N = x.shape[:2]
+    B = x.shape[2] if x.dim() == 3 else 1
+    tail = tuple(x.shape[2:])
+    shape_col, shape_row = (max(M - 1, 0), N) + tail, (M, max(N - 1, 0)) + tail
+    if weights_col is not None:
+        _check(weights_col, "weights_col", like=x, shape=shape_col)
+        _check(weights_row, "weights_row", like=x, shape=shape_row)
+    dx = _tangent(dx, "dx", x, x.shape)
+    dweights_col = _tangent(dweights_col, "dweights_col", x, shape_col)
+    dweights_row = _tangent(dweights_row, "dweights_row", x, shape_row)
+    w_row = w_col if w_row is None else w_row
+    dy = colmajor_empty(x.shape, device=x.device)
+    y = colmajor_empty(x.shape, device=x.device) if need_y else None
+    ptr = lambda t: t.data_ptr() if t is not None and t.numel() else 0   # noqa: E731
+    # (a weight map without edges -- M == 1 or N == 1 -- has no storage: any non-null address says "weighted", nothing is read through it)
+    wptr = lambda t: 0 if t is None else (ptr(t) or x.data_ptr())        # noqa: E731
+    with torch.cuda.device(x.device):
+        lib = _lib.require_device()
+        lib.proxtv_DR2_TV_jvp_dev(M, N, B, ptr(x), float(w_col), float(w_row), wptr(weights_col), wptr(weights_row), ptr(dx),
+                                  ptr(dweights_col), ptr(dweights_row), float(dw_col), float(dw_row), ptr(y), ptr(dy), int(max_iters),
+                                  _stream(x.device))
+    _lib.check("device.dr2_jvp")
+    return dy, y
+
+
 def _cotangent(g, x):
     if not (isinstance(g, torch.Tensor) and g.is_cuda and g.dtype == torch.float64):
         raise ValueError("g: expected a float64 CUDA tensor")
